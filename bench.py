@@ -2,6 +2,11 @@
 """Throughput of the MI355X ByteTrack update() (BASELINE.json headline metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--n 1024]
+                    [--dump-outputs DIR] [--full]
+
+A plain run stages the frames, warms up, times the K steps and prints the headline line (`value`,
+`ms_per_step`, ...); `--dump-outputs DIR` also writes what the last timed step returned
+(dump_outputs).  Every other leg below runs only with `--full`.
 
 A step = one `tracker.update()` frame for every one of the S independent streams on each GPU
 (each stream: 1024 tracks x 1024 detections per frame, SURVEY.md §8(d) synthetic generator).
@@ -18,7 +23,10 @@ environment) or directly as `bench.py --gpus N`: the parent then starts N rank p
 process per sequence and device.  `--dry-cpu` runs the same harness on CPU ranks over gloo with a
 NumPy stand-in step (tests/test_bench_harness.py).
 
-Rank 0 prints one JSON line with `roofline` (the longest launch of the isolated leg - engine 0
+More than `--timed-window` (64) steps replay the staged timed frames forwards and backwards
+(window_frame), so staging time and HBM do not grow with the step count.
+
+Rank 0 prints one JSON line; with `--full` it also holds `roofline` (the longest launch of the isolated leg - engine 0
 alone after the timed region - by HIP events on its stream, with its measured HBM bytes from the
 committed rocprofv3 PMC summary, per kernel),
 `pcie_inclusive` (host buffers in and out every call) and `cpu_baseline` (the oracle's CPU
@@ -197,6 +205,17 @@ def parse(argv=None):
                         "BASELINE config (C2-C5) as the measured workload, streams sharded s mod "
                         "G over the ranks (tools/bench_tracker.py engines)")
     p.add_argument("--dim", type=int, default=512, help="embedding width (ReID trackers)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline: the isolated leg (roofline, per_kernel), the "
+                        "host-buffer (PCIe) legs, the drop-in leg, configs C2-C5 and the CPU "
+                        "baseline; the --no-* options below each skip one of these legs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (output "
+                        "rows and counts, DUMP_STREAMS sampled streams) as DIR/<name>.npy")
+    p.add_argument("--timed-window", type=int, default=64,
+                   help="distinct timed frames staged in HBM; a run of more --steps than this "
+                        "plays the window forwards and backwards (staging time and HBM stay "
+                        "bounded), a run of at most this many steps never repeats a frame")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-pcie", action="store_true", help="skip the host-buffer (PCIe) leg")
     p.add_argument("--pcie-engines", type=int, default=1,
@@ -218,6 +237,10 @@ def parse(argv=None):
     p.add_argument("--dry-cpu", action="store_true",
                    help="harness rehearsal: CPU ranks over gloo, NumPy stand-in step, no GPU")
     a = p.parse_args(argv)
+    if a.dump_outputs and (a.tracker != "bytetrack" or a.dry_cpu):
+        p.error("--dump-outputs writes the ByteTrack headline's outputs (no --tracker, --dry-cpu)")
+    if a.timed_window < 2:
+        p.error("--timed-window must be at least 2")
     if a.tracker == "bytetrack":
         a.streams = 2048 if a.streams is None else a.streams
         a.n = 1024 if a.n is None else a.n
@@ -308,33 +331,138 @@ def gen_stream_frames(n, frames, seed):
     return [d for d, _ in make_frames(n, frames, seed)]
 
 
-def stage_frames(n, frames, seeds, Q, device):
+def _fill_frame(gens, n, out):
+    """Advance every generator one frame into out[k*n:(k+1)*n]."""
+    for k, g in enumerate(gens):
+        d, _ = g.next_frame()
+        assert len(d) == n, "synthetic frames have N detections per stream"
+        out[k * n:(k + 1) * n] = d
+
+
+def _stage_worker(raw, n, seeds, lo, total, frames, free, done):
+    """One generator process of host_frames: streams lo .. lo + len(seeds) - 1 of every frame, into
+    slot f % 2 of the shared two-frame buffer."""
+    # synth.py by its path: it needs NumPy alone; importing the package would load torch here too
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "_yta_synth", os.path.join(REPO, "yolo_tracking_amd", "synth.py"))
+    synth = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(synth)
+    slots = np.frombuffer(raw, dtype=np.float64).reshape(2, total * n, 6)
+    gens = [synth.SyntheticStream(n, sd) for sd in seeds]
+    for f in range(frames):
+        free.acquire()
+        _fill_frame(gens, n, slots[f % 2, lo * n:(lo + len(seeds)) * n])
+        done.release()
+
+
+def host_frames(n, frames, seeds, host, workers=None):
+    """Generator: fills `host` ([S*N][6] float64) with frame f of every stream and yields f, for
+    f = 0 .. frames - 1.  Stream s is SyntheticStream(n, seeds[s]) whatever the worker count: with
+    more than one worker the streams are split over that many generator processes (started fresh,
+    they never touch the GPU), which write a shared two-frame buffer one frame ahead of the
+    reader.  workers: default this job's CPU share, at most 16."""
+    from yolo_tracking_amd.synth import SyntheticStream
+    S = len(seeds)
+    P = min(cpu_share(), 16) if workers is None else workers
+    P = max(1, min(P, S // 8))          # a process is not worth fewer than 8 streams
+    if P == 1 or frames == 0:
+        gens = [SyntheticStream(n, sd) for sd in seeds]
+        for f in range(frames):
+            _fill_frame(gens, n, host)
+            yield f
+        return
+    import multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    raw = ctx.RawArray("d", 2 * S * n * 6)
+    slots = np.frombuffer(raw, dtype=np.float64).reshape(2, S * n, 6)
+    bounds = [S * w // P for w in range(P + 1)]
+    free = [ctx.Semaphore(2) for _ in range(P)]
+    done = [ctx.Semaphore(0) for _ in range(P)]
+    procs = [ctx.Process(target=_stage_worker, daemon=True,
+                         args=(raw, n, seeds[bounds[w]:bounds[w + 1]], bounds[w], S, frames,
+                               free[w], done[w])) for w in range(P)]
+    for p in procs:
+        p.start()
+    try:
+        for f in range(frames):
+            for w in range(P):
+                while not done[w].acquire(timeout=5):
+                    if not procs[w].is_alive():
+                        raise RuntimeError(f"frame generator {w} exited with "
+                                           f"{procs[w].exitcode} at frame {f}")
+            host[:] = slots[f % 2]
+            for w in range(P):
+                free[w].release()
+            yield f
+        for p in procs:
+            p.join()
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+                p.join()
+
+
+def stage_frames(n, frames, seeds, Q, device, workers=None):
     """Synthetic frames of this rank's streams straight into HBM, one frame at a time: every
-    stream's generator advances one frame into a page-locked [S*N][6] buffer, which is copied into
-    each engine's [frames][S/Q*N][6] device tensor.  Host memory stays at one frame of every
-    stream (no per-stream frame lists, no stacked copy), whatever the step count or rank count.
+    stream's generator advances one frame into a page-locked [S*N][6] buffer (host_frames), which
+    is copied into each engine's [frames][S/Q*N][6] device tensor.  Host memory stays at a few
+    frames of every stream (no per-stream frame lists, no stacked copy), whatever the step count
+    or rank count.
     Returns (per-engine device tensors, per-engine device offset tensors [frames][S/Q + 1])."""
     import torch
 
-    from yolo_tracking_amd.synth import SyntheticStream
     S = len(seeds)
     Sq = S // Q
-    gens = [SyntheticStream(n, sd) for sd in seeds]
     buf = torch.empty((S * n, 6), dtype=torch.float64, pin_memory=True)
     host = buf.numpy()
     d_dets = [torch.empty((frames, Sq * n, 6), dtype=torch.float64, device=device)
               for _ in range(Q)]
-    for f in range(frames):
-        for s, g in enumerate(gens):
-            d, _ = g.next_frame()
-            assert len(d) == n, "synthetic frames have N detections per stream"
-            host[s * n:(s + 1) * n] = d
+    for f in host_frames(n, frames, seeds, host, workers):
         for q in range(Q):
             d_dets[q][f].copy_(buf[q * Sq * n:(q + 1) * Sq * n])
     torch.cuda.synchronize()
     off = torch.arange(Sq + 1, dtype=torch.int32) * n
     d_off = [off.repeat(frames, 1).contiguous().to(device) for _ in range(Q)]
     return d_dets, d_off
+
+
+def window_frame(k, window):
+    """Timed step k -> index into the `window` staged timed frames: 0 .. window-1, then back down
+    to 0 and up again (adjacent steps are always adjacent frames of the stream, in either
+    direction).  k < window: k itself."""
+    period = 2 * (window - 1)
+    j = k % period if period else 0
+    return j if j < window else period - j
+
+
+DUMP_STREAMS = 256        # --dump-outputs: streams sampled (256 x 2048 rows x 64 B = 32 MiB)
+DUMP_BYTES = 48 << 20     # ... and the cap on the sampled rows for other --n / --streams
+
+
+def dump_outputs(directory, d_out, d_cnt, cap, seed, rank):
+    """--dump-outputs: what the device-buffer update wrote in the last timed step, as float64
+    .npy files: `counts` (S,) the output rows of every stream of this rank, `sample_streams` (K,)
+    a fixed seeded sample of the streams (sorted; all of them when they fit), `rows` (K, cap, 8)
+    the sampled streams' output rows [x1, y1, x2, y2, id, conf, cls, det_ind], rows past a
+    stream's count zeroed.  d_out / d_cnt: the engines' output buffers in stream order.  Ranks
+    above 0 write <name>_rank<r>.npy."""
+    import torch
+    counts = torch.cat(d_cnt).cpu().numpy()
+    S = len(counts)
+    K = min(S, DUMP_STREAMS, max(1, DUMP_BYTES // (cap * 64)))
+    pick = np.sort(np.random.default_rng(seed).choice(S, size=K, replace=False))
+    Sq = S // len(d_out)
+    rows = np.zeros((K, cap, 8), dtype=np.float64)
+    for i, s in enumerate(pick):
+        q, j = divmod(int(s), Sq)
+        c = int(counts[s])
+        rows[i, :c] = d_out[q][j * cap:j * cap + c].cpu().numpy()
+    os.makedirs(directory, exist_ok=True)
+    tail = "" if rank == 0 else f"_rank{rank}"
+    for name, arr in (("counts", counts), ("sample_streams", pick), ("rows", rows)):
+        np.save(os.path.join(directory, f"{name}{tail}.npy"), np.asarray(arr, dtype=np.float64))
 
 
 _CPU_LEG = (
@@ -719,7 +847,7 @@ def run_config(args, world, rank, local_rank):
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     line = config_shard_leg(args.tracker, args.n, args.dim, args.streams, args.steps, args.warmup,
                             args.seed, world, rank, dist, "cpu" if args.shared_gpu else "cuda",
-                            cpu=world == 1 and not args.no_cpu_baseline)
+                            cpu=args.full and world == 1 and not args.no_cpu_baseline)
     if rank == 0:
         line.update(higher_is_better=True, vs_baseline=None, dtype="f64", data="synthetic",
                     config={"workload": line.pop("workload"), "tracker": args.tracker,
@@ -763,11 +891,12 @@ def main():
     from yolo_tracking_amd import ByteTrackEngine, _lib
     S, N = args.streams, args.n
     PRE = args.preroll + args.warmup          # untimed frames before the timed region
-    F = PRE + args.steps
+    W = min(args.steps, args.timed_window)    # distinct timed frames (window_frame)
+    F = PRE + W
     Q = max(1, args.queues)
-    # with Q > 1 engines, ISO more frames after the timed region run on engine 0 alone: the
-    # roofline kernel's launch with the chip to itself (never part of `value`)
-    ISO = 3 if Q > 1 and not args.no_isolated else 0
+    # --full with Q > 1 engines: ISO more frames after the timed region run on engine 0 alone:
+    # the roofline kernel's launch with the chip to itself (never part of `value`)
+    ISO = 3 if args.full and Q > 1 and not args.no_isolated else 0
     FT = F + ISO
     # synthetic frames for this rank's streams, staged in HBM one frame at a time:
     # Q x [FT][S/Q*N][6] + offsets
@@ -809,12 +938,16 @@ def main():
     for hq in handles:
         _lib.check(lib.yta_bytetrack_profile(hq, 1))
 
+    timed = [PRE + window_frame(k, W) for k in range(args.steps)]
+
     def run_steps():
-        for f in range(PRE, F):
+        for f in timed:
             step(f)
         sync_all()
 
     elapsed = timed_region(run_steps, torch.cuda.synchronize, dist)
+    if args.dump_outputs:   # before the isolated leg reuses engine 0's output buffer
+        dump_outputs(args.dump_outputs, d_out, d_cnt, cap, args.seed, rank)
     # per-launch phase times: engine 0's HIP events (with Q > 1 they overlap the other engines')
     ms = (ctypes.c_double * len(PHASES))()
     nfr = ctypes.c_int()
@@ -852,7 +985,7 @@ def main():
     # configs as BASELINE.json states them); one failing rank would leave the others at a barrier,
     # so a failure is reported, not raised, and the legs run only while every rank is healthy
     multi_cfg = None
-    if world > 1 and not args.no_configs:
+    if args.full and world > 1 and not args.no_configs:
         multi_cfg = {}
         for name, tr, n, sp, stp, wu in MULTI_CONFIGS:
             try:
@@ -862,7 +995,33 @@ def main():
                 multi_cfg[name] = {"value": None, "error": repr(exc)[:300]}
 
     st_launch = {k: v // Q for k, v in st.items()}   # one engine's launch (Q equal slices)
-    if rank == 0:
+    # the headline: all a plain run prints; --full adds the other legs to this line
+    head = {
+        "metric": "tracker.update() calls/sec @ 1024 tracks×1024 dets; 1/2/4/8 MI355X",
+        "value": value, "unit": "calls/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"bytetrack {N}x{N}, {S} streams/GPU, inputs resident in HBM",
+                   "tracker": "bytetrack", "tracks": N, "dets": N, "streams_per_gpu": S,
+                   "queues_per_gpu": Q, "parallelism": f"stream-sharded x{world}",
+                   "untimed_frames": PRE, "preroll": args.preroll,
+                   "timed_frames": (f"{PRE + 1}..{F}" if W == args.steps else
+                                    f"{PRE + 1}..{F} forwards and backwards, {args.steps} steps"),
+                   "per_stream_last_frame": {
+                       "pool": st["pool"] / S, "tracked": st["tracked"] / S,
+                       "lost": st["lost"] / S, "births": st["births"] / S,
+                       "out_rows": st["out"] / S},
+                   "value_is": "device-resident: frames staged in HBM before the timed "
+                               "region, output rows left in HBM; the host-buffer rate "
+                               "(dets in, rows out over PCIe every call) is pcie_inclusive "
+                               "(--full)"},
+        "frame_counts": st,
+        "stage_seconds": round(gen_s, 1),
+        "host_peak_rss_mb_by_rank": rss,
+    }
+    if rank == 0 and not args.full:
+        print(json.dumps(head))
+    if rank == 0 and args.full:
         traffic, step_traffic, traffic_tag = pmc_traffic(S, N, Q)
         # Roofline kernel: the launch with the largest share of the timed step (engine 0's HIP
         # events in the timed region).  Its achieved rate comes from the isolated leg (engine 0
@@ -930,22 +1089,7 @@ def main():
             dropin["vs_cpu_1core"] = dropin["value"] / cpu["value"]
         dk = traffic.get(PHASE_KERNEL[dom], {})
         line = {
-            "metric": "tracker.update() calls/sec @ 1024 tracks×1024 dets; 1/2/4/8 MI355X",
-            "value": value, "unit": "calls/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"bytetrack {N}x{N}, {S} streams/GPU, inputs resident in HBM",
-                       "tracker": "bytetrack", "tracks": N, "dets": N, "streams_per_gpu": S,
-                       "queues_per_gpu": Q, "parallelism": f"stream-sharded x{world}",
-                       "untimed_frames": PRE, "preroll": args.preroll,
-                       "timed_frames": f"{PRE + 1}..{F}",
-                       "per_stream_last_frame": {
-                           "pool": st["pool"] / S, "tracked": st["tracked"] / S,
-                           "lost": st["lost"] / S, "births": st["births"] / S,
-                           "out_rows": st["out"] / S},
-                       "value_is": "device-resident: frames staged in HBM before the timed "
-                                   "region, output rows left in HBM; the host-buffer rate "
-                                   "(dets in, rows out over PCIe every call) is pcie_inclusive"},
+            **head,
             "roofline": {"bound": "hbm", "kernel": PHASE_KERNEL[dom], "achieved": achieved,
                          "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS,
@@ -993,7 +1137,6 @@ def main():
             "configs": configs,
             "per_kernel": per_kernel,
             "per_kernel_overlapped": overlapped,
-            "frame_counts": st,
             "busiest_kernel": dom,
             "kernel_bytes_note": "per_kernel.alg_bytes: bench.kernel_bytes (every array element a "
                                  "launch must read or write once, from the frame's counts); "
@@ -1006,8 +1149,6 @@ def main():
                                       "(dense_upper_bound) charges a dense 16*N*M cost matrix "
                                       "and a 576-B Kalman state that this build never forms",
             "dense_upper_bound_bytes_per_update": algorithmic_bytes(N, N),
-            "stage_seconds": round(gen_s, 1),
-            "host_peak_rss_mb_by_rank": rss,
         }
         print(json.dumps(line))
     if dist:

@@ -112,6 +112,42 @@ def test_config_seeds_shard_mod_g():
     assert all(all(x % G == r for x in every[r]) for r in range(G))
 
 
+def test_window_frame_plays_forwards_and_backwards():
+    """Steps beyond the staged window walk it back and forth: adjacent steps are adjacent frames,
+    every index stays inside the window, and a run that fits never repeats a frame."""
+    assert [bench.window_frame(k, 4) for k in range(10)] == [0, 1, 2, 3, 2, 1, 0, 1, 2, 3]
+    assert [bench.window_frame(k, 2) for k in range(4)] == [0, 1, 0, 1]
+    assert [bench.window_frame(k, 1) for k in range(3)] == [0, 0, 0]
+    assert [bench.window_frame(k, 64) for k in range(64)] == list(range(64))
+    idx = [bench.window_frame(k, 7) for k in range(100)]
+    assert min(idx) == 0 and max(idx) == 6
+    assert all(abs(a - b) == 1 for a, b in zip(idx, idx[1:]))
+
+
+def test_host_frames_same_from_generator_processes():
+    """bench.host_frames: the frames are the streams' SyntheticStream frames whether one process
+    generates them or several (odd stream count: uneven split)."""
+    import numpy as np
+
+    from yolo_tracking_amd.synth import make_frames
+    n, frames, seeds = 24, 4, list(range(500, 519))
+    exp = [np.concatenate([make_frames(n, frames, sd)[f][0] for sd in seeds])
+           for f in range(frames)]
+    for workers in (1, 2):
+        host = np.empty((len(seeds) * n, 6))
+        got = [host.copy() for _ in bench.host_frames(n, frames, seeds, host, workers)]
+        assert len(got) == frames
+        for f in range(frames):
+            assert np.array_equal(got[f], exp[f]), (workers, f)
+
+
+def test_bench_plain_by_default():
+    a = bench.parse([])
+    assert not a.full and a.dump_outputs is None and a.timed_window == 64
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
 def test_bench_defaults_per_tracker():
     a = bench.parse([])
     assert (a.tracker, a.n, a.streams) == ("bytetrack", 1024, 2048)

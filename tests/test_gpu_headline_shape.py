@@ -40,7 +40,7 @@ SQ = S // Q
 SEED = 1000
 PRE = 35 + 5          # bench.py --preroll 35 + the driver's --warmup 5
 STEPS = 20            # the driver's --steps 20
-ISO = 3               # bench.py's isolated leg: engine 0 alone
+ISO = 3               # bench.py --full's isolated leg: engine 0 alone
 F = PRE + STEPS
 FT = F + ISO
 CAP = 2 * N           # bench.py: track_capacity 2N, max_dets N

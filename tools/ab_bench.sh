@@ -12,7 +12,7 @@ for r in $(seq ${ROUNDS:-2}); do
   for lib in "$@"; do
     for q in ${QUEUES:-1 2}; do
       if [ "$lib" = default ]; then L=""; else L="$R/$lib"; fi
-      YTA_LIBRARY=$L timeout -k 10 300 python3 $R/bench.py --queues $q --steps 20 --warmup 5 --no-cpu-baseline --no-pcie --no-isolated > $O/b.json 2> $O/b.err || { echo "FAIL $lib q$q" >> $out; cat $O/b.err | tail -5; exit 1; }
+      YTA_LIBRARY=$L timeout -k 10 300 python3 $R/bench.py --queues $q --full --steps 20 --warmup 5 --no-cpu-baseline --no-pcie --no-isolated > $O/b.json 2> $O/b.err || { echo "FAIL $lib q$q" >> $out; cat $O/b.err | tail -5; exit 1; }
       python3 - "$lib" "$q" "$O/b.json" >> $out <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[3]).read().strip().splitlines()[-1])

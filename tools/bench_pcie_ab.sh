@@ -9,7 +9,7 @@ cd $R
 n=0
 for cfg in "$@"; do
   n=$((n+1))
-  env $cfg timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-configs --no-dropin \
+  env $cfg timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --no-configs --no-dropin \
       --no-cpu-baseline > $O/$n.json 2> $O/$n.err || exit $?
   python3 - "$cfg" $O/$n.json <<'PY'
 import json, sys

@@ -11,6 +11,6 @@ echo "pytest rc=$rc"; tail -3 $O/pytest.log
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit $?
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 python3 $R/bench.py > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 400 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
 cat $O/bench.json
 echo done
