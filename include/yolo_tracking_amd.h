@@ -103,6 +103,12 @@ int yta_kf_xyah_update(int device, int n, double *mean, double *cov, const doubl
  * cross-lane operations) at several block sizes.  0 when every result matches a serial answer. */
 int yta_selftest(int device);
 
+/* Host evaluation (no device needed) of the block placement k_apply uses (xcd_stream_blocks,
+ * csrc/common.hpp): for a launch of gx blocks per stream over n_streams streams, stream[lin] /
+ * block[lin] = the logical (stream, block) that hardware block lin = blockIdx.x + gx * blockIdx.y
+ * works on; both arrays hold gx * n_streams ints. */
+int yta_apply_block_map(int gx, int n_streams, int *stream, int *block);
+
 /* ---- linear assignment with lapx cost_limit semantics -------------------------------------
  * Minimises sum(matched cost) + cost_limit/2 * (#unmatched rows + #unmatched cols); x[r] = col or
  * -1, y[c] = row or -1 (lap.lapjv(cost, extend_cost=True, cost_limit=cost_limit)). */

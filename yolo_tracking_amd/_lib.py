@@ -135,6 +135,7 @@ _SIGS = {
     "yta_bytetrack_hip_stream": ([_P, _P], _I),
     "yta_bytetrack_set_lds": ([_P, _I], _I),
     "yta_selftest": ([_I], _I),
+    "yta_apply_block_map": ([_I, _I, _P, _P], _I),
     "yta_botsort_create": ([_I, _I, _I, _I, _I, _P, _P], _I),
     "yta_botsort_update": ([_P, _P, _P, _P, _P, _P, _P, _I, _P], _I),
     "yta_botsort_update_device": ([_P, _P, _P, _P, _P, _P, _P], _I),

@@ -1734,6 +1734,9 @@ __device__ __forceinline__ void take_detection(const BtArgs &a, KfState &st, Tra
 // pieces of a record (full-line reads and writes); each thread then runs the Kalman step of one
 // track out of LDS.  LDS row: pieces 0-3 the mean, 4-6 the meta, 7-14 the covariance (record
 // pieces 0-6 and 8-15: the padding piece 7 is skipped).
+#ifndef YTA_APPLY_XCD
+#define YTA_APPLY_XCD 1   // k_apply: the blocks of a stream share an XCD (xcd_stream_blocks); 0: launch order
+#endif
 constexpr int APPLY_T = 128;              // tracks (= threads) per block
 constexpr int REC_PIECES = 15;            // 16-B pieces of a record that carry data
 constexpr int L_META = 8, L_COV = 14;     // doubles: meta / covariance in an LDS row
@@ -1746,11 +1749,16 @@ __global__ __launch_bounds__(APPLY_T) void k_apply(BtArgs a) {
     static_assert(APPLY_T % WAVE == 0, "whole waves per block (LDS-direct load tiling)");
     __shared__ int s_slot[APPLY_T];
     __shared__ int s_wmask[APPLY_T];      // bit 0: write the Kalman record, bit 1: write the meta
-    const int s = blockIdx.y, t = threadIdx.x;
+    // logical (stream, block) of this workgroup: a stream's blocks on one XCD (common.hpp)
+    int s = blockIdx.y, bx = blockIdx.x;
+#if YTA_APPLY_XCD
+    xcd_stream_blocks(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x, gridDim.y, s, bx);
+#endif
+    const int t = threadIdx.x;
     if (stream_skipped(a, s)) return;
     BtCounters *c = a.cnt + s;
     const int n_pool = c->n_pool, n_unc = c->n_unc, fid = c->frame_id;
-    const int i0 = blockIdx.x * APPLY_T;
+    const int i0 = bx * APPLY_T;
     const int n_items = n_pool + n_unc;
     if (i0 >= n_items) return;                                       // block-uniform
     YTA_APL(0);

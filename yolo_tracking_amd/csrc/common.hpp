@@ -73,6 +73,27 @@ __device__ __forceinline__ void xcd_tile(int &bx, int &by) {
     }
 }
 
+// XCD-aware placement of a (gx blocks per stream) x (S streams) grid whose blocks of one stream
+// read the same per-stream arrays (k_apply: the stream's detection rows and match lists).  In
+// launch order stream s's blocks have linear ids gx * s + x and land on all 8 XCDs, so every L2
+// fetches the stream's lines for itself.  Instead linear id lin goes to XCD lin & 7 as its
+// (lin >> 3)-th block, and that XCD walks the streams s = xcd, xcd + 8, ... with the gx blocks of
+// one stream back to back: a stream's blocks share one L2, and s & 7 is the XCD the
+// one-block-per-stream kernels (blockIdx.x = s) put that stream on.  The streams of the last
+// partial group of 8 (S not a multiple of 8) keep the launch order, so the map is a bijection of
+// [0, gx * S) for every gx, S.  Placement is a hint: nothing may depend on it but speed.
+__host__ __device__ __forceinline__ void xcd_stream_blocks(int lin, int gx, int S, int &s, int &b) {
+    const int S8 = S & ~7;
+    if (lin < gx * S8) {
+        const int xcd = lin & 7, k = lin >> 3;
+        s = (k / gx) * 8 + xcd;
+        b = k % gx;
+    } else {
+        s = lin / gx;
+        b = lin % gx;
+    }
+}
+
 // Diagnostic build only (-DYTA_STAMPS, tools/diag_stamps.py): wall-clock stamps (100 MHz) of
 // block 0's phases, read back with yta_debug_stamps.
 #ifdef YTA_STAMPS

@@ -73,4 +73,11 @@ int yta_device_count(int *count) {
     return YTA_OK;
 }
 
+int yta_apply_block_map(int gx, int n_streams, int *stream, int *block) {
+    YTA_CHECK(gx > 0 && n_streams > 0 && stream && block, YTA_ERR_INVALID, "bad block map shape");
+    for (int lin = 0; lin < gx * n_streams; ++lin)
+        yta::xcd_stream_blocks(lin, gx, n_streams, stream[lin], block[lin]);
+    return YTA_OK;
+}
+
 }  // extern "C"
