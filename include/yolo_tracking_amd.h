@@ -283,6 +283,54 @@ int yta_bytetrack_set_lds(yta_bytetrack *engine, int bytes);
 /* Throughput helper: the engine's HIP stream (hipStream_t as void*) */
 int yta_bytetrack_hip_stream(yta_bytetrack *engine, void **stream);
 
+/* Tensor path: one frame of all S streams from device rows to device rows, stream-ordered, for a
+ * detector that runs on the same device.  Results equal yta_bytetrack_update's, bit for bit, on
+ * the same values.
+ *   Stream order.  caller_stream is a hipStream_t (NULL: the legacy default stream).  The call
+ *     returns without waiting for the device.  What it enqueues runs on the engine's own stream,
+ *     after everything queued on caller_stream at the time of the call; on return caller_stream
+ *     has been made to wait for the frame's last launch, so later work on it sees the outputs and
+ *     may free or overwrite the inputs.  Work on any OTHER stream needs its own ordering.
+ *     A caller_stream that is being captured into a graph is refused (YTA_ERR_INVALID).
+ *   In.  d_dets: rows [x1, y1, x2, y2, conf, cls] of dtype (YTA_F64 / YTA_F32 / YTA_F16),
+ *     row_stride elements apart (>= 6: a column slice of a wider tensor is fine, any alignment of
+ *     whole elements), stream 0's det_counts[0] rows first, then stream 1's, ...  float32 and
+ *     float16 values are promoted exactly, as the reference promotes float32
+ *     (byte_tracker.py:143).  A 16-byte aligned float64 tensor with row_stride 6 is read in
+ *     place; anything else is widened into the engine's staging by one launch, which also turns
+ *     det_counts into the device offsets.  det_counts: S ints in HOST memory.  next_id: S counters
+ *     in HOST memory written to the device before the frame, or NULL to continue the engine's
+ *     own; both are copied during the call and reusable at once.  d_active: S ints on the device,
+ *     nonzero = update that stream (see yta_bytetrack_update_device_masked), or NULL.
+ *   Out.  d_rows (16-byte aligned, rows_capacity >= sum(det_counts) rows x 8 float64) receives the
+ *     packed [x1,y1,x2,y2,id,conf,cls,det_ind] rows, stream after stream; d_row_offsets (S + 1
+ *     ints) delimit the streams; d_row_stream (rows_capacity ints, may be NULL) holds each row's
+ *     stream id and -1 from d_row_offsets[S] on.  Rows past d_row_offsets[S] are unspecified.
+ *     Nothing is copied to the host.
+ *   Capacity.  Both capacities grow as needed before anything is enqueued, so the frame never
+ *     raises the device's capacity flags.  max_dets follows det_counts.  Track capacity is bounded
+ *     on the host: the live tracks after the newest tensor frame known to have run (its kernels
+ *     store them into page-locked memory) plus every detection enqueued since.  If
+ *     track_capacity >= live tracks + every detection enqueued since the caller last synchronised
+ *     the engine, no call waits for the device (host_waits below stays 0); otherwise the call
+ *     waits for the engine's stream, reads the exact counters and grows the engine if they
+ *     require it.  Frames fed through yta_bytetrack_update_device in between are not counted.
+ *   Mixing.  The synchronous entry points wait for the tensor frames in flight and see their
+ *     state; device error flags are reported by the next call that synchronises
+ *     (yta_bytetrack_sync).  With pipelined frames in flight the call fails with YTA_ERR_INVALID.
+ */
+#define YTA_F64 0
+#define YTA_F32 1
+#define YTA_F16 2
+int yta_bytetrack_update_tensors(yta_bytetrack *engine, void *caller_stream, const void *d_dets,
+                                 int dtype, long long row_stride, const int *det_counts,
+                                 const int *d_active, const long long *next_id, double *d_rows,
+                                 long long rows_capacity, int *d_row_offsets, int *d_row_stream);
+/* Accounting of the tensor path (writes min(n, 4) int64, also for BoT-SORT engines): frames
+ * enqueued; host_waits, the calls that blocked on the device; reserves, the times the engine
+ * grew; ingest_skipped, the frames whose float64 rows were read in place. */
+int yta_bytetrack_tensor_stats(yta_bytetrack *engine, long long *out, int n);
+
 /* ---- BoT-SORT engine: S independent streams ----------------------------------------------
  * The same engine object as ByteTrack (yta_bytetrack_destroy / reset / reserve / capacity / sync /
  * get_state / profile / stats / set_lds / hip_stream all apply; get_state's mean is xywh) with
@@ -319,6 +367,18 @@ int yta_botsort_update(yta_botsort *engine, const double *dets, const int *det_o
 int yta_botsort_update_device(yta_botsort *engine, const double *d_dets, const int *d_det_offsets,
                               const float *d_feats, const double *d_warps, double *d_out,
                               int *d_out_counts);
+/* Tensor path (see yta_bytetrack_update_tensors for the stream order, the inputs, the outputs and
+ * the capacity rules).  d_feats: one feat_dim-wide float32 row per DETECTION row, feat_stride
+ * floats apart (>= feat_dim; NULL when with_reid is 0); only the rows of detections with
+ * conf > track_high_thresh are read, so the others may hold anything.  d_warps: S row-major 2x3
+ * warps on the device or NULL for the identity, as yta_botsort_update_device.  The host never sees
+ * the warps, so it cannot refuse non-finite entries as yta_botsort_update does: finite warps are
+ * the caller's responsibility. */
+int yta_botsort_update_tensors(yta_botsort *engine, void *caller_stream, const void *d_dets,
+                               int dtype, long long row_stride, const int *det_counts,
+                               const float *d_feats, long long feat_stride, const double *d_warps,
+                               const int *d_active, const long long *next_id, double *d_rows,
+                               long long rows_capacity, int *d_row_offsets, int *d_row_stream);
 /* Subset update (see yta_bytetrack_update_streams): feats cover the listed streams' high
  * detections in id order, warps n_streams 2x3 affines (or NULL). */
 int yta_botsort_update_streams(yta_botsort *engine, int n_streams, const int *stream_ids,

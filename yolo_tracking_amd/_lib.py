@@ -94,6 +94,12 @@ _lib = None
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _D = ctypes.c_double
+_LL = ctypes.c_longlong
+
+# dtype codes of device detection rows (yta_bytetrack_update_tensors)
+YTA_F64 = 0
+YTA_F32 = 1
+YTA_F16 = 2
 
 _SIGS = {
     "yta_version": ([], _I),
@@ -134,6 +140,10 @@ _SIGS = {
     "yta_bytetrack_modes": ([_P, _P, _I], _I),
     "yta_bytetrack_hip_stream": ([_P, _P], _I),
     "yta_bytetrack_set_lds": ([_P, _I], _I),
+    "yta_bytetrack_update_tensors": ([_P, _P, _P, _I, _LL, _P, _P, _P, _P, _LL, _P, _P], _I),
+    "yta_bytetrack_tensor_stats": ([_P, _P, _I], _I),
+    "yta_botsort_update_tensors": ([_P, _P, _P, _I, _LL, _P, _P, _LL, _P, _P, _P, _P, _LL, _P, _P],
+                                   _I),
     "yta_selftest": ([_I], _I),
     "yta_apply_block_map": ([_I, _I, _P, _P], _I),
     "yta_botsort_create": ([_I, _I, _I, _I, _I, _P, _P], _I),

@@ -196,11 +196,13 @@ class ReIDDetectMultiBackend:
             ctypes.c_void_p(work.data_ptr()), self._stream()))
         return features
 
-    def get_features(self, xyxys, img):
-        """:303-311: features of the crops, divided by their global norm (NumPy (N, D))."""
+    def get_features(self, xyxys, img, as_tensor=False):
+        """:303-311: features of the crops, divided by their global norm (NumPy (N, D)).
+        as_tensor: hand the same normalised features back as a device tensor instead (the
+        trackers' tensor path, where the embeddings never leave HBM)."""
         torch = self.torch
         if np.asarray(xyxys).size == 0:
-            return np.array([])
+            return torch.empty((0, 0), device=self.device) if as_tensor else np.array([])
         with torch.no_grad():
             crops = self.preprocess(xyxys, img)
             if self.model is None:
@@ -210,4 +212,4 @@ class ReIDDetectMultiBackend:
                 f = f[0]
             dt = f.dtype
             f = self.normalize_(f.float().contiguous())
-            return f.to(dt).cpu().numpy()
+            return f.to(dt) if as_tensor else f.to(dt).cpu().numpy()

@@ -1,0 +1,144 @@
+"""Plumbing of the tensor path (yta_bytetrack_update_tensors / yta_botsort_update_tensors): checks
+the caller's device tensors, lays them out as the C ABI wants them and allocates the outputs.
+Everything here is host-side bookkeeping or a torch call on the caller's stream; no value is read
+back from the device.  Anything wrong raises ValueError before a single launch.
+"""
+import ctypes
+
+import numpy as np
+
+from .. import _lib
+
+
+def is_cuda_tensor(x):
+    """True for a torch tensor in device memory, without importing torch for anything else."""
+    return type(x).__module__.split(".")[0] == "torch" and bool(getattr(x, "is_cuda", False))
+
+
+def _dtype_codes(torch):
+    return {torch.float64: _lib.YTA_F64, torch.float32: _lib.YTA_F32, torch.float16: _lib.YTA_F16}
+
+
+def _check(torch, t, name, device, cols, dtypes):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: expected a torch tensor, got {type(t).__name__}")
+    if not t.is_cuda or t.device.index != device:
+        raise ValueError(f"{name}: tensor on {t.device}, the engine runs on cuda:{device}")
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError(f"{name}: expected shape (n, {cols}), got {tuple(t.shape)}")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{name}: dtype {t.dtype} is none of "
+                         f"{', '.join(str(d) for d in dtypes)}")
+
+
+def _rows(torch, parts, counts, n_streams, name, device, cols, dtypes):
+    """One (total, cols) tensor and the S per-stream row counts from either a list of S tensors
+    or one tensor + counts.  Checks only; the concatenation happens in `prepare`."""
+    if isinstance(parts, (list, tuple)):
+        if counts is not None:
+            raise ValueError(f"{name}: counts go with one packed tensor, not with a list")
+        if len(parts) != n_streams:
+            raise ValueError(f"{name}: {len(parts)} tensors for {n_streams} streams")
+        for k, t in enumerate(parts):
+            _check(torch, t, f"{name}[{k}]", device, cols, dtypes)
+        if len({t.dtype for t in parts}) != 1:
+            raise ValueError(f"{name}: the streams' tensors differ in dtype")
+        return list(parts), np.array([t.shape[0] for t in parts], dtype=np.int32)
+    _check(torch, parts, name, device, cols, dtypes)
+    if counts is None:
+        if n_streams != 1:
+            raise ValueError(f"{name}: one packed tensor for {n_streams} streams needs counts")
+        counts = [parts.shape[0]]
+    c = np.asarray(counts, dtype=np.int64).reshape(-1)
+    if len(c) != n_streams or (c < 0).any():
+        raise ValueError(f"counts: expected {n_streams} non-negative entries, got {c.tolist()}")
+    if int(c.sum()) != parts.shape[0]:
+        raise ValueError(f"counts sum to {int(c.sum())}, {name} has {parts.shape[0]} rows")
+    return parts, np.ascontiguousarray(c, dtype=np.int32)
+
+
+def _pack(torch, rows, min_stride):
+    """The checked rows as one tensor whose columns are adjacent and whose rows are a fixed
+    stride >= min_stride apart (a column slice of a wider tensor passes as it is)."""
+    t = (rows[0] if len(rows) == 1 else torch.cat(rows)) if isinstance(rows, list) else rows
+    if t.shape[0] and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < min_stride)):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), min_stride))
+
+
+class TensorFrame:
+    """One frame's checked inputs and fresh outputs, ready for the C call."""
+
+    def __init__(self, engine, dets, counts, active, next_id, stream, feats=None, warps=None):
+        import torch
+        self.torch = torch
+        S, dev = engine.n_streams, engine.device
+        codes = _dtype_codes(torch)
+        # ---- checks first: nothing is allocated or enqueued for a frame that is refused
+        dets, self.counts = _rows(torch, dets, counts, S, "dets", dev, 6, tuple(codes))
+        total = int(self.counts.sum())
+        D = getattr(engine, "feat_dim", 0)
+        if D:
+            if feats is None:
+                raise ValueError("feats: this engine runs with ReID features")
+            feats, fc = _rows(torch, feats, None if isinstance(feats, (list, tuple))
+                              else self.counts, S, "feats", dev, D, (torch.float32,))
+            if not np.array_equal(fc, self.counts):
+                raise ValueError("feats: one row per detection row is needed, got "
+                                 f"{fc.tolist()} rows for {self.counts.tolist()} detections")
+        if active is not None:
+            if not isinstance(active, torch.Tensor) or not active.is_cuda or \
+                    active.device.index != dev or tuple(active.shape) != (S,) or \
+                    active.dtype not in (torch.int32, torch.int64, torch.bool, torch.uint8):
+                raise ValueError(f"active: expected an integer or bool ({S},) tensor on cuda:{dev}")
+        if warps is not None:
+            if isinstance(warps, torch.Tensor):
+                if not warps.is_cuda or warps.device.index != dev or warps.numel() != 6 * S or \
+                        warps.dtype != torch.float64:
+                    raise ValueError(f"warps: expected float64 ({S}, 2, 3) on cuda:{dev}")
+            else:
+                warps = np.ascontiguousarray(warps, dtype=np.float64)
+                if warps.size != 6 * S:
+                    raise ValueError(f"warps: expected ({S}, 2, 3), got {warps.shape}")
+        self.nid = None
+        if next_id is not None:
+            self.nid = np.ascontiguousarray(next_id, dtype=np.int64).reshape(-1)
+            if len(self.nid) != S:
+                raise ValueError(f"next_id: expected {S} counters, got {len(self.nid)}")
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        self.stream = stream
+        # ---- layout and outputs, all on the caller's stream
+        with torch.cuda.stream(stream):
+            self.dets, self.row_stride = _pack(torch, dets, 6)
+            self.dtype = codes[self.dets.dtype]
+            self.feats, self.feat_stride = (None, 0)
+            if D:
+                self.feats, self.feat_stride = _pack(torch, feats, D)
+            self.active = None
+            if active is not None:
+                self.active = active.to(torch.int32).contiguous()
+            self.warps = None
+            if warps is not None:
+                if not isinstance(warps, torch.Tensor):
+                    warps = torch.from_numpy(warps.reshape(S, 6)).to(self.dets.device)
+                self.warps = warps.reshape(S, 6).contiguous()
+            d = self.dets.device
+            self.rows = torch.empty((total, 8), dtype=torch.float64, device=d)
+            self.offsets = torch.empty(S + 1, dtype=torch.int32, device=d)
+            self.row_stream = torch.empty(total, dtype=torch.int32, device=d)
+
+    @staticmethod
+    def _p(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+    def common_head(self):
+        return (ctypes.c_void_p(self.stream.cuda_stream), self._p(self.dets), self.dtype,
+                int(self.row_stride), _lib.ptr(self.counts))
+
+    def common_tail(self):
+        return (self._p(self.active), _lib.ptr(self.nid), self._p(self.rows), self.rows.shape[0],
+                ctypes.c_void_p(self.offsets.data_ptr()), self._p(self.row_stream))
+
+    def result(self):
+        return self.rows, self.offsets, self.row_stream

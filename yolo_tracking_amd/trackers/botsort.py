@@ -14,12 +14,14 @@ it to the predicted pool and the unconfirmed tracks as STrack.multi_gmc does (bo
 290-295).
 """
 import ctypes
+import inspect
 
 import numpy as np
 
 from .. import _lib
 from ..appearance import build_reid
 from ..motion.cmc import IdentityCMC, default_cmc
+from ._tensors import is_cuda_tensor
 from .bytetrack import ByteTrackEngine, STrackView
 
 
@@ -139,6 +141,21 @@ class BoTSORTEngine(ByteTrackEngine):
         self._subset_check(rc, order, nid, nid_user)
         return self._subset_result(o, order)
 
+    def update_tensors(self, dets, feats=None, warps=None, counts=None, active=None, next_id=None,
+                       stream=None):
+        """ByteTrackEngine.update_tensors for BoT-SORT (yta_botsort_update_tensors).  feats: one
+        float32 feat_dim-wide row per DETECTION row (a list of S (M_s, D) CUDA tensors or one
+        (total, D) tensor); only the rows of detections with conf > track_high_thresh are read,
+        the others may hold anything.  warps: optional (S, 2, 3) float64 CUDA tensor (or host
+        array, copied on the stream); non-finite entries are the caller's responsibility here,
+        since the host never sees a device tensor's values."""
+        from ._tensors import TensorFrame
+        f = TensorFrame(self, dets, counts, active, next_id, stream, feats=feats, warps=warps)
+        _lib.check(self.lib.yta_botsort_update_tensors(
+            self._h, *f.common_head(), f._p(f.feats), int(f.feat_stride), f._p(f.warps),
+            *f.common_tail()))
+        return f.result()
+
     def features(self, stream=0):
         """Smoothed features, class histograms (n, 8, 2) and their entry counts of the live
         tracks, in state() order."""
@@ -212,7 +229,61 @@ class BoTSORT:
             self._engine.update([np.zeros((0, 6))], [None])   # they only advanced frame_id
         self._empty_frames = 0
 
+    def _update_tensor(self, dets, img, embs):
+        """update() for a CUDA tensor of detections (embs, when given, a CUDA tensor with one row
+        per detection): the embeddings and the rows stay on the device.  Only the high boxes go
+        to the host, for the crops and the camera-motion estimate, which take host frames."""
+        import torch
+        assert isinstance(img, np.ndarray), \
+            f"Unsupported 'img_numpy' input format '{type(img)}', valid format is np.ndarray"
+        assert dets.dim() == 2, "Unsupported 'dets' dimensions, valid number of dimensions is two"
+        assert dets.shape[1] == 6, "Unsupported 'dets' 2nd dimension lenght, valid lenghts is 6"
+        self.frame_id += 1
+        # compared as float64, like the engine and the ndarray path (:266-267)
+        high = dets[:, 4].double() > self.track_high_thresh
+        high_rows = dets[high].double().cpu().numpy()
+        feats = None
+        if self.with_reid and len(high_rows):                    # :270-271
+            if embs is not None:
+                if not is_cuda_tensor(embs) or embs.dim() != 2 or len(embs) != len(dets):
+                    raise ValueError("embs: with tensor dets, a CUDA tensor with one row per "
+                                     "detection is needed")
+                feats = embs.float()
+            else:
+                if self.model is None:
+                    raise RuntimeError(
+                        "BoTSORT(with_reid=True) needs a ReID producer: pass reid=<object with "
+                        "get_features(xyxys, img)> or update(dets, img, embs=...)")
+                # ReIDDetectMultiBackend keeps them in HBM; a producer without as_tensor hands
+                # NumPy rows, which are uploaded
+                if "as_tensor" in inspect.signature(self.model.get_features).parameters:
+                    f = self.model.get_features(high_rows[:, 0:4], img, as_tensor=True).float()
+                else:
+                    f = torch.from_numpy(np.asarray(self.model.get_features(
+                        high_rows[:, 0:4], img), np.float32)).to(dets.device)
+                feats = torch.zeros((len(dets), f.shape[1]), dtype=torch.float32,
+                                    device=dets.device)
+                feats[high] = f
+            if self._engine is None:
+                self._make_engine(feats.shape[1])
+        warp = np.asarray(self.cmc.apply(img, high_rows), dtype=np.float64)   # :299
+        if self._engine is None:                                  # no high detection yet
+            self._empty_frames += 1
+            return dets.new_zeros((0, 8), dtype=torch.float64)
+        if feats is None and self._engine.feat_dim:   # no high row: none is read
+            feats = torch.zeros((len(dets), self._engine.feat_dim), dtype=torch.float32,
+                                device=dets.device)
+        self._nid[0] = BaseTrack._count
+        rows, off, _ = self._engine.update_tensors([dets], feats, warps=warp[None],
+                                                   next_id=self._nid)
+        BaseTrack._count = int(self._engine.next_ids()[0])   # waits: the frame has run
+        return rows[:int(off[1])]
+
     def update(self, dets, img, embs=None):
+        """dets: np.ndarray (N, 6) as the reference; a CUDA tensor (N, 6) is taken where it is
+        (embs then a CUDA tensor too) and the (K, 8) result is then a CUDA tensor."""
+        if is_cuda_tensor(dets):
+            return self._update_tensor(dets, img, embs)
         assert isinstance(dets, np.ndarray), \
             f"Unsupported 'dets' input format '{type(dets)}', valid format is np.ndarray"
         assert isinstance(img, np.ndarray), \

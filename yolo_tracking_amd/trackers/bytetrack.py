@@ -11,6 +11,7 @@ import numpy as np
 
 from .. import _lib
 from ._streams import StreamSubset
+from ._tensors import is_cuda_tensor
 from .basetrack import BaseTrack, TrackState
 
 
@@ -165,6 +166,46 @@ class ByteTrackEngine(StreamSubset):
             next_id[...] = nid
         return [out[o[s]:o[s + 1]].copy() for s in range(self.n_streams)]
 
+    def update_tensors(self, dets, counts=None, active=None, next_id=None, stream=None):
+        """Stream-ordered update from device tensors to device tensors
+        (yta_bytetrack_update_tensors): nothing crosses the link and nothing is waited for.
+        dets: a list of S CUDA tensors (M_s, 6), or one (total, 6) tensor (a column slice of a
+        wider tensor is passed with its row stride) with `counts`, the S per-stream row counts
+        (host ints); float64, float32 or float16, promoted exactly.  active: optional (S,)
+        integer / bool CUDA tensor, nonzero = update that stream.  next_id: optional host int64
+        (S,) counters written before the frame (not updated: read next_ids() after a
+        synchronisation).  stream: the torch stream the inputs were produced on and the outputs
+        are consumed on (default: the current one).
+        Returns (rows (total, 8) float64, offsets (S + 1,) int32, row_stream (total,) int32) on
+        the engine's device: stream s's rows are rows[offsets[s]:offsets[s + 1]], row_stream[r] is
+        row r's stream and -1 from offsets[S] on.  Results equal update()'s bit for bit.
+        Raises ValueError, before anything is enqueued, for tensors on another device or of the
+        wrong shape or dtype."""
+        from ._tensors import TensorFrame
+        f = TensorFrame(self, dets, counts, active, next_id, stream)
+        _lib.check(self.lib.yta_bytetrack_update_tensors(self._h, *f.common_head(),
+                                                         *f.common_tail()))
+        return f.result()
+
+    def tensor_stats(self):
+        """Accounting of update_tensors (yta_bytetrack_tensor_stats): frames enqueued, calls that
+        blocked on the device, engine growths, float64 frames read in place."""
+        names = ["frames", "host_waits", "reserves", "ingest_skipped"]
+        buf = (ctypes.c_longlong * len(names))()
+        _lib.check(self.lib.yta_bytetrack_tensor_stats(self._h, buf, len(names)))
+        return {k: int(buf[i]) for i, k in enumerate(names)}
+
+    def next_ids(self):
+        """The S per-stream ID counters on the device (waits for the engine's stream)."""
+        nid = np.zeros(self.n_streams, dtype=np.int64)
+        _lib.check(self.lib.yta_bytetrack_next_ids(self._h, _lib.ptr(nid)))
+        return nid
+
+    def sync(self):
+        """Wait for the engine's stream; raises if a frame since the last wait set a device
+        error flag."""
+        _lib.check(self.lib.yta_bytetrack_sync(self._h))
+
     def state(self, stream=0):
         """Live tracks of one stream (tracked list then lost list) for parity checks."""
         cap, _ = self.capacity()
@@ -224,7 +265,22 @@ class BYTETracker:
                                        device=device)
         self._nid = np.zeros(1, dtype=np.int64)
 
+    def _update_tensor(self, dets):
+        """update() for a CUDA tensor of detections: the rows stay on the device.  One wait per
+        call, to learn K and to keep the process-global BaseTrack._count."""
+        assert dets.dim() == 2, "Unsupported 'dets' dimensions, valid number of dimensions is two"
+        assert dets.shape[1] == 6, "Unsupported 'dets' 2nd dimension lenght, valid lenghts is 6"
+        self.frame_id += 1
+        self._nid[0] = BaseTrack._count
+        rows, off, _ = self._engine.update_tensors([dets], next_id=self._nid)
+        BaseTrack._count = int(self._engine.next_ids()[0])   # waits: the frame has run
+        return rows[:int(off[1])]
+
     def update(self, dets, _=None):
+        """dets: np.ndarray (N, 6) as the reference; a CUDA tensor (N, 6) is taken where it is
+        and the (K, 8) result is then a CUDA tensor too."""
+        if is_cuda_tensor(dets):
+            return self._update_tensor(dets)
         assert isinstance(dets, np.ndarray), \
             f"Unsupported 'dets' input format '{type(dets)}', valid format is np.ndarray"
         assert len(dets.shape) == 2, \
