@@ -4,8 +4,9 @@
 
     python tools/pipe_timeline.py <trace dir> [--last N]
 
-A frame = one k_s1_prep launch (its kernels run k_s1_prep .. k_cnt_to_host on the compute stream);
-its copy-in is the last host->device copy of >= 1 MB that ends before its k_s1_prep starts, its
+A frame = one launch of its first kernel (k_s1_edges, or k_s1_prep where that is still launched;
+its kernels run from there to k_cnt_to_host on the compute stream);
+its copy-in is the last host->device copy of >= 1 MB that ends before that kernel starts, its
 copy-out the k_rows_to_host launch (or device->host copy) that starts after its k_cnt_to_host.
 Prints, per frame (ms, relative to the first frame's copy-in start): copy-in start / end, kernels
 start / end, copy-out start / end, the wait between the copy-in end and the first kernel, and the
@@ -15,6 +16,11 @@ import argparse
 import csv
 import glob
 import os
+
+
+# a frame's first kernel: k_s1_edges opens the frame unless the library was built with
+# -DYTA_FUSE_DETS=0, where k_s1_prep's launch precedes it
+FIRST = ("k_s1_prep", "k_s1_edges")
 
 
 def rows(d, pat):
@@ -35,9 +41,10 @@ def main():
                  if "HOST_TO_DEVICE" in r["Direction"])
     d2h = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in mc
                  if "DEVICE_TO_HOST" in r["Direction"])
+    first = next((n for n in FIRST if any(n in k[2] for k in ks)), FIRST[0])
     frames = []
     for i, k in enumerate(ks):
-        if "k_s1_prep" not in k[2]:
+        if first not in k[2]:
             continue
         end = None
         for k2 in ks[i:]:

@@ -510,18 +510,20 @@ __global__ __launch_bounds__(SPLIT ? BLK23S : BLK23) void k_redo_stage23(BtArgs 
 }
 
 // ------------------------------------------------------------------ ByteTrack stage 1, split
-// k_stage1's work for ByteTrack (match_thresh <= 1) as three launches that keep several streams
+// k_stage1's work for ByteTrack (match_thresh <= 1) as two launches (three with
+// -DYTA_FUSE_DETS=0: k_s1_prep's own launch, the sequence up to DESIGN 13.10) that keep several streams
 // on every CU (the fused kernel holds one 1024-thread stream per CU, its 150 KiB arena, for the
 // whole latency chain of the frame).  Under load a dependent HBM round trip costs microseconds,
 // so every pass issues all of a thread's loads before using any, and hand-offs that go through
 // LDS only do not drain global stores (lds_sync):
 //   k_s1_prep  [block/stream, 256 thr, 32 KiB static LDS] detection pass and confidence split
-//              (:149-158), tracked -> activated / unconfirmed, pool = act ++ lost with predicted
-//              boxes (:169-178, multi_predict's mean :35-48); coalesced loads, items staged in
-//              LDS per pass (holding a run of items per thread in registers measured 1.6x slower:
-//              strided rows, uncoalesced stores)
-//   k_s1_edges [block/stream, 512 thr, <= 58 KiB LDS] grid over the high detections built in
-//              LDS from two register-held detections per thread, then every pool row's candidate
+//              (:149-158; s1_dets_pass: items staged in LDS per pass), launched only with
+//              -DYTA_FUSE_DETS=0.  (The pool = act ++ lost with predicted boxes, :169-178, is
+//              built by the previous frame's k_finish, or by k_pool_build after a reserve.)
+//   k_s1_edges [block/stream, 512 thr, <= 62 KiB LDS] the detection pass from registers
+//              (s1_dets_fused: two rows per thread, one packed scan, lists to HBM, the high
+//              boxes handed to their list positions' threads through LDS), the grid over the
+//              high detections built in LDS from those registers, then every pool row's candidate
 //              edges, fused IoU cost (:181-183, matching.py:117, :216-220) below match_thresh:
 //              count + the first E_SLOTS edges to HBM (the grid goes to HBM too when some row
 //              has more)
@@ -660,24 +662,49 @@ __global__ __launch_bounds__(PREP_T) void k_pool_build(BtArgs a) {
     s1_pool_build(a, s, sh);
 }
 
-// NT: PREP_T, or 1024 with few streams (split23: one block per stream takes the lists)
-template <int NT>
-__global__ __launch_bounds__(NT) void k_s1_prep(BtArgs a) {
-    __shared__ PrepShared sh;
-    const int s = blockIdx.x, t = threadIdx.x;
-    if (stream_skipped(a, s)) return;
-    YTA_STAMP_BASE(60);
-    YTA_STAMP(0);
-    YTA_BLK(0, 0);
-    BtCounters *c = a.cnt + s;
-    const long long db = (long long)s * a.MAXD;
+// The detection pass of a frame (one block per stream): STrack conversions, the confidence split
+// into the order-preserving high / second lists, then the frame's counters.  It runs as its own
+// launch (k_s1_prep -> s1_dets_pass) or, with YTA_FUSE_DETS, at the top of k_s1_edges from
+// registers (s1_dets_fused); both forms share the pieces below, and write the same lists.
+#ifndef YTA_FUSE_DETS
+#define YTA_FUSE_DETS 1   // 0: k_s1_prep's own launch ahead of k_s1_edges (the A/B build)
+#endif
+
+// The stream's detection count, clamped to the capacity (ERR_DET_CAPACITY when it was not within)
+__device__ __forceinline__ int s1_det_count(const BtArgs &a, int s) {
     int nd = a.det_off[s + 1] - a.det_off[s];
     if (nd > a.MAXD || nd < 0) {
-        if (t == 0) atomicOr(&c->err, ERR_DET_CAPACITY);
+        if (threadIdx.x == 0) atomicOr(&a.cnt[s].err, ERR_DET_CAPACITY);
         nd = nd < 0 ? 0 : a.MAXD;
     }
+    return nd;
+}
+
+// byte_tracker.py:149-158: 1 high, 2 second, 0 neither (a NaN confidence is neither)
+__device__ __forceinline__ int s1_det_cat(const BtArgs &a, double conf) {
+    return conf > a.track_thresh ? 1 : (conf > a.low_thresh && conf < a.track_thresh ? 2 : 0);
+}
+
+// Thread 0, after the lists: the pool (n_act / n_unc / n_pool) was built by the last k_finish
+__device__ __forceinline__ void s1_frame_counters(BtCounters *c, int nd, int n_high, int n_second) {
+    if (threadIdx.x != 0) return;
+    c->frame_id += 1;
+    c->n_dets = nd;
+    c->n_high = n_high;
+    c->n_second = n_second;
+    c->n_left = 0;
+    c->n_rest = 0;
+    c->n_births = 0;
+    c->n_lazy = 0;
+    c->n_res1 = 0;
+    c->n_ref = 0;
+}
+
+__device__ __forceinline__ void s1_dets_pass(const BtArgs &a, int s, PrepShared &sh) {
+    BtCounters *c = a.cnt + s;
+    const long long db = (long long)s * a.MAXD;
+    const int nd = s1_det_count(a, s);
     const double *din = a.det_in + (long long)a.det_off[s] * 6;
-    const double thr = a.track_thresh;
     // detections, PREP_CH per pass (coalesced loads, 3 rows in flight per thread): STrack
     // conversions (:16-18), measurement, confidence split (:149-158), boxes staged in LDS, then
     // the order-preserving high / second lists
@@ -697,7 +724,7 @@ __global__ __launch_bounds__(NT) void k_s1_prep(BtArgs a) {
                 double xywh[4];
                 det_xyxy_to_xywh(r.v, xywh);
                 const double conf = r.v[4];
-                sh.u.d.cat[i] = conf > thr ? 1 : (conf > a.low_thresh && conf < thr ? 2 : 0);
+                sh.u.d.cat[i] = s1_det_cat(a, conf);
                 sh.u.d.box[i] = xywh_to_box(xywh);
 #if YTA_PREP_CH <= 768
                 sh.u.d.conf[i] = conf;
@@ -727,20 +754,109 @@ __global__ __launch_bounds__(NT) void k_s1_prep(BtArgs a) {
         lds_sync();   // the staging area is reused
     }
     YTA_STAMP(1);
-    if (t == 0) {   // the pool (n_act / n_unc / n_pool) was built by the last k_finish
-        c->frame_id += 1;
-        c->n_dets = nd;
-        c->n_high = n_high;
-        c->n_second = n_second;
-        c->n_left = 0;
-        c->n_rest = 0;
-        c->n_births = 0;
-        c->n_lazy = 0;
-        c->n_res1 = 0;
-        c->n_ref = 0;
-    }
+    s1_frame_counters(c, nd, n_high, n_second);
+}
+
+// NT: PREP_T, or 1024 with few streams (split23: one block per stream takes the lists)
+template <int NT>
+__global__ __launch_bounds__(NT) void k_s1_prep(BtArgs a) {
+    __shared__ PrepShared sh;
+    const int s = blockIdx.x;
+    if (stream_skipped(a, s)) return;
+    YTA_STAMP_BASE(60);
+    YTA_STAMP(0);
+    YTA_BLK(0, 0);
+    s1_dets_pass(a, s, sh);
     YTA_STAMP(3);
     YTA_BLK(0, 1);
+}
+
+// Exclusive block scans of two values at once (one barrier pair).  wsum: 32 ints.
+__device__ __forceinline__ void block_exclusive_scan_pair(int x, int y, int *wsum, int &ex, int &ey,
+                                                          int &tx, int &ty) {
+    const int lane = lane_id(), wid = threadIdx.x / WAVE, nw = blockDim.x / WAVE;
+    const int ix = wave_inclusive_scan(x), iy = wave_inclusive_scan(y);
+    if (lane == WAVE - 1) {
+        wsum[wid] = ix;
+        wsum[16 + wid] = iy;
+    }
+    lds_sync();
+    const int px = wave_inclusive_scan(lane < nw ? wsum[lane] : 0);
+    const int py = wave_inclusive_scan(lane < nw ? wsum[16 + lane] : 0);
+    ex = ix - x + (wid > 0 ? __builtin_amdgcn_readlane(px, wid - 1) : 0);
+    ey = iy - y + (wid > 0 ? __builtin_amdgcn_readlane(py, wid - 1) : 0);
+    tx = __builtin_amdgcn_readlane(px, nw - 1);
+    ty = __builtin_amdgcn_readlane(py, nw - 1);
+    __syncthreads();   // wsum is reused by the next scan
+}
+
+// The detection pass inside k_s1_edges: thread t takes rows c0 + t and c0 + t + blockDim of each
+// chunk of 2 blockDim rows into registers, and one packed scan per chunk (high | second << 16, the
+// chunk's two halves side by side) gives every row its place in detection order - the lists
+// block_compact2 writes in s1_dets_pass.  One chunk (nd <= 2 blockDim) is the shape the
+// register-held grid build needs: then `hand` (hand_cap bytes of LDS; 5 arrays of n_high doubles)
+// gets the high boxes and scores by list position, for the thread that owns position j (handed;
+// false when the pass took several chunks or the area is too small).  Returns n_high; the caller
+// syncs (LDS for `hand`, block_sync before anything reads the lists from global memory).
+__device__ __forceinline__ int s1_dets_fused(const BtArgs &a, int s, int *wsum, double *hand,
+                                             long long hand_cap, bool &handed) {
+    const int t = threadIdx.x, nt = blockDim.x;
+    const long long db = (long long)s * a.MAXD;
+    const int nd = s1_det_count(a, s);
+    const double *din = a.det_in + (long long)a.det_off[s] * 6;
+    int n_high = 0, n_second = 0;
+    handed = false;
+    for (int c0 = 0; c0 < nd; c0 += 2 * nt) {   // block-uniform trip count
+        const int i0 = c0 + t, i1 = i0 + nt;
+        DetRow r[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {   // unconditional loads (rows past nd load the last row)
+            const double *d = din + (long long)((h ? i1 : i0) < nd ? (h ? i1 : i0) : nd - 1) * 6;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) r[h].v[k] = d[k];
+        }
+        Box b[2];
+        int cat[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            double xywh[4];
+            det_xyxy_to_xywh(r[h].v, xywh);
+            b[h] = xywh_to_box(xywh);
+            cat[h] = (h ? i1 : i0) < nd ? s1_det_cat(a, r[h].v[4]) : 0;
+        }
+        int e0, e1, t0, t1;
+        block_exclusive_scan_pair((cat[0] == 1) | ((cat[0] == 2) << 16),
+                                  (cat[1] == 1) | ((cat[1] == 2) << 16), wsum, e0, e1, t0, t1);
+        const int nh = (t0 & 0xFFFF) + (t1 & 0xFFFF), ns = (t0 >> 16) + (t1 >> 16);
+        // the whole pass in one chunk, and the lists' boxes fit the hand-off area
+        const bool give = nd <= 2 * nt && 5LL * 8 * nh <= hand_cap;
+        handed = give;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int e = h ? t0 + e1 : e0;   // packed: rows of the first half come first
+            if (cat[h] == 1) {
+                const int p = n_high + (e & 0xFFFF);
+                a.high[db + p] = h ? i1 : i0;
+                a.high_box[db + p] = b[h];
+                a.high_score[db + p] = r[h].v[4];
+                if (give) {
+                    hand[p] = b[h].x1;
+                    hand[nh + p] = b[h].y1;
+                    hand[2 * nh + p] = b[h].x2;
+                    hand[3 * nh + p] = b[h].y2;
+                    hand[4 * nh + p] = r[h].v[4];
+                }
+            } else if (cat[h] == 2) {
+                const int p = n_second + (e >> 16);
+                a.second[db + p] = h ? i1 : i0;
+                a.second_box[db + p] = b[h];
+            }
+        }
+        n_high += nh;
+        n_second += ns;
+    }
+    s1_frame_counters(a.cnt + s, nd, n_high, n_second);
+    return n_high;
 }
 
 // Every candidate edge of pool row box rb: f(high position, fused IoU cost) for cost <
@@ -1063,23 +1179,54 @@ __global__ __launch_bounds__(NT, NT == BLKE ? 4 : 1) void k_s1_edges(BtArgs a) {
     YTA_BLK(1, 0);
     BtCounters *c = a.cnt + s;
     const long long db = (long long)s * a.MAXD;
-    const int nc = c->n_high, nr = c->n_pool;
-    // this thread's detections t and t + blockDim held in registers (nc <= 2 blockDim: every box
-    // load in flight at once; the grid build reads them three times)
-    Box hb0{0.0, 0.0, 0.0, 0.0}, hb1{0.0, 0.0, 0.0, 0.0};
-    double hw0 = 0.0, hw1 = 0.0;
-    if (t < nc) {
-        hb0 = a.high_box[db + t];
-        hw0 = a.high_score[db + t];
-    }
-    if (t + nt < nc) {
-        hb1 = a.high_box[db + t + nt];
-        hw1 = a.high_score[db + t + nt];
-    }
     if (t == 0) {
         spill = 0;
         n_edges = 0;
     }
+    // this thread's high detections t and t + blockDim held in registers (nc <= 2 blockDim; the
+    // grid build reads them three times)
+    Box hb0{0.0, 0.0, 0.0, 0.0}, hb1{0.0, 0.0, 0.0, 0.0};
+    double hw0 = 0.0, hw1 = 0.0;
+#if YTA_FUSE_DETS
+    // The frame's detection pass first (k_s1_prep's work): the lists go to HBM for the later
+    // kernels, and the high boxes reach their list positions' threads through the arena, which is
+    // free until the grid is built.  The area overlaps the grid arrays: it is dead (second
+    // lds_sync) before grid_build or cdeg write them.
+    double *hand = reinterpret_cast<double *>(smem);
+    bool handed;
+    const int nc = s1_dets_fused(a, s, wsum, hand, (long long)a.lds_bytes_e, handed);
+    const int nr = c->n_pool;
+    YTA_STAMP(3);
+    if (handed) {
+        lds_sync();
+        if (t < nc) {
+            hb0 = Box{hand[t], hand[nc + t], hand[2 * nc + t], hand[3 * nc + t]};
+            hw0 = hand[4 * nc + t];
+        }
+        if (t + nt < nc) {
+            hb1 = Box{hand[t + nt], hand[nc + t + nt], hand[2 * nc + t + nt], hand[3 * nc + t + nt]};
+            hw1 = hand[4 * nc + t + nt];
+        }
+        lds_sync();
+    } else {
+        block_sync();   // the lists this block stored are read back below
+#else
+    const int nc = c->n_high, nr = c->n_pool;
+    {
+#endif
+        // every box load in flight at once
+        if (t < nc) {
+            hb0 = a.high_box[db + t];
+            hw0 = a.high_score[db + t];
+        }
+        if (t + nt < nc) {
+            hb1 = a.high_box[db + t + nt];
+            hw1 = a.high_score[db + t + nt];
+        }
+    }
+    // Both grid paths below read high_box / high_score from global memory (big items, the HBM
+    // grid's build): with the fused pass these are this block's own stores, and every such read
+    // follows a block_sync (the HBM path's own, grid_build's on the LDS path).
     int rn[4] = {0, 0, 0, 0}, rc[4] = {-1, -1, -1, -1};   // rows t + b * nt (s1_single_edges)
     if (nc > 2 * nt || s1_grid_bytes(nc) + 4LL * nc > (long long)a.lds_bytes_e) {   // HBM grid
         int *cdeg = a.g_deg + db;
@@ -3242,7 +3389,8 @@ int set_lds_limits(size_t bytes) {
     return YTA_OK;
 }
 
-// One frame of every stream: 6 launches (ByteTrack), 4 + k_feat and k_ema (BoT-SORT, fused stage
+// One frame of every stream: 5 launches (ByteTrack; 6 with -DYTA_FUSE_DETS=0, else phase s1_prep
+// is an empty interval and s1_edges holds the detection pass), 4 + k_feat and k_ema (BoT-SORT, fused stage
 // 1); with more streams than pooled fallback arenas each association kernel is followed by its
 // redo kernel (ws_slots blocks that return at once unless a stream fell back).  Profiling marks bracket the phases s1_prep / s1_edges / s1_lap (BoT-SORT: k_feat + k_stage1,
 // empty, empty), stage23, apply (k_apply + k_ema), finish.
@@ -3268,11 +3416,13 @@ int launch_frame(yta_bytetrack *e) {
         YTA_HIP(hipGetLastError());
     }
     if (V == VAR_BYTETRACK && a.match_thresh <= 1.0) {   // grid-exact candidates (assoc.hpp)
+#if !YTA_FUSE_DETS   // else k_s1_edges opens with the detection pass: phase s1_prep is empty
         if (e->split23)
             hipLaunchKernelGGL(k_s1_prep<1024>, dim3(a.S), dim3(1024), 0, e->stream, a);
         else
             hipLaunchKernelGGL(k_s1_prep<PREP_T>, dim3(a.S), dim3(PREP_T), 0, e->stream, a);
         YTA_HIP(hipGetLastError());
+#endif
         MARK();
         if (e->split23)
             hipLaunchKernelGGL(k_s1_edges<1024>, dim3(a.S), dim3(1024), a.lds_bytes_e, e->stream, a);
