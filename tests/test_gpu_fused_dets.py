@@ -1,4 +1,4 @@
-"""The detection pass at the top of k_s1_edges (csrc/bytetrack.hip, s1_dets_fused; YTA_FUSE_DETS):
+"""The detection pass at the top of k_s1_edges (csrc/bytetrack.hip, s1_dets_fused):
 thread t classifies detection rows t and t + blockDim from registers, one packed block scan gives
 the order-preserving high / second list positions, the lists go to HBM and the high boxes reach
 the grid build through LDS.  More than 2 * blockDim detections take the chunked form and the

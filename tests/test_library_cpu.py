@@ -35,6 +35,26 @@ def test_missing_library_fails_loudly(tmp_path):
         _lib.load_library(str(tmp_path / "nope.so"))
 
 
+def test_makefile_hdrs_lists_every_included_header():
+    """Every object depends on HDRS (csrc/Makefile), so a quoted include missing from it leaves
+    stale objects behind an edit of that header; and an entry that does not exist stops make."""
+    csrc = os.path.join(REPO, "yolo_tracking_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
+    hdrs = re.search(r"^HDRS\s*=(.*)$", mk, re.M).group(1).split()
+    assert len(hdrs) == len(set(hdrs))
+    for h in hdrs:
+        assert os.path.isfile(os.path.join(csrc, h)), h
+    listed = {os.path.normpath(h) for h in hdrs}
+    sources = glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp"))
+    assert len(sources) > 20
+    included = 0
+    for path in sources:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
+            assert os.path.normpath(inc) in listed, f"{os.path.basename(path)} includes {inc}"
+            included += 1
+    assert included > 20
+
+
 def test_plugin_surface():
     import yolo_tracking_amd as y
     assert y.TRACKERS == ['bytetrack', 'botsort', 'strongsort', 'ocsort', 'deepocsort',

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Diagnostic: per-phase stamps (block 0) of ByteTrack's split stage 1 (k_s1_prep, when it is
-launched, / k_s1_edges / k_s1_lap) and of k_stage23 / k_finish, from the -DYTA_STAMPS library that tools/diag_stamps.py
---build compiles.   python tools/diag_s1.py [--streams 1024] [--frames 25]   (GPU)"""
+"""Diagnostic: per-phase stamps (block 0) of ByteTrack's split stage 1 (k_s1_edges / k_s1_lap)
+and of k_stage23 / k_finish, from the -DYTA_STAMPS library that tools/diag_stamps.py --build
+compiles.   python tools/diag_s1.py [--streams 1024] [--frames 25]   (GPU)"""
 import argparse
 import ctypes
 import os
@@ -48,8 +48,7 @@ def main():
     _lib.check(lib.yta_debug_stamps(st.ctypes.data))
     st = st.astype(np.int64)
     print("stats", eng.stats())
-    show(st, 60, {1: "dets pass", 2: "tracked pass", 3: "lost pass + counters"}, "k_s1_prep")
-    # the detection pass runs inside k_s1_edges (stamp 3) unless built with -DYTA_FUSE_DETS=0
+    # the detection pass runs inside k_s1_edges (stamp 3)
     show(st, 66, {3: "dets pass", 1: "grid build", 2: "pool queries"}, "k_s1_edges")
     show(st, 90, {1: "row offsets", 2: "csr fill", 8: "lap init", 9: "lap P1 union",
                   10: "lap P2 roots", 11: "lap P3 lists", 12: "lap P4 gather",

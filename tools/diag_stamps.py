@@ -99,9 +99,8 @@ def main():
                       (10, "lap P2 roots"), (11, "lap P3 lists"), (12, "lap P4 gather"),
                       (13, "lap classify"), (14, "lap solve"), (3, "lap return"),
                       (4, "results out")], "k_bs_lap")
-    elif st[60] or st[66]:   # ByteTrack: stage 1 as (k_s1_prep /) k_s1_edges / k_s1_lap
-        # the detection pass runs inside k_s1_edges (stamp 3) unless built with -DYTA_FUSE_DETS=0
-        show(st, 60, {1: "dets pass", 2: "tracked pass", 3: "lost pass"}, "k_s1_prep")
+    elif st[66]:   # ByteTrack: stage 1 as k_s1_edges / k_s1_lap
+        # the detection pass runs inside k_s1_edges (stamp 3)
         show(st, 66, {3: "dets pass", 1: "grid build", 2: "edges"}, "k_s1_edges")
         show(st, 90, [(1, "row offsets"), (2, "CSR fill"), (8, "lap init"), (9, "lap P1 union"),
                       (10, "lap P2 roots"), (11, "lap P3 lists"), (12, "lap P4 gather"),
@@ -131,8 +130,7 @@ def main():
     _lib.check(lib.yta_debug_blocks(blk.ctypes.data))
     blk = blk.reshape(8, 4096, 2).astype(np.int64)[:, :S]
     print("-- per-block timeline (us; start relative to the kernel's first block start)")
-    for k, name in [(0, "k_s1_prep"), (1, "k_s1_edges"), (2, "k_s1_lap"), (3, "k_stage23"),
-                    (5, "k_finish")]:
+    for k, name in [(1, "k_s1_edges"), (2, "k_s1_lap"), (3, "k_stage23"), (5, "k_finish")]:
         b0, b1 = blk[k, :, 0], blk[k, :, 1]
         if not b0.any():
             continue

@@ -4,8 +4,8 @@
 
     python tools/pipe_timeline.py <trace dir> [--last N]
 
-A frame = one launch of its first kernel (k_s1_edges, or k_s1_prep where that is still launched;
-its kernels run from there to k_cnt_to_host on the compute stream);
+A frame = one launch of its first kernel (k_s1_edges; its kernels run from there to k_cnt_to_host
+on the compute stream);
 its copy-in is the last host->device copy of >= 1 MB that ends before that kernel starts, its
 copy-out the k_rows_to_host launch (or device->host copy) that starts after its k_cnt_to_host.
 Prints, per frame (ms, relative to the first frame's copy-in start): copy-in start / end, kernels
@@ -18,9 +18,8 @@ import glob
 import os
 
 
-# a frame's first kernel: k_s1_edges opens the frame unless the library was built with
-# -DYTA_FUSE_DETS=0, where k_s1_prep's launch precedes it
-FIRST = ("k_s1_prep", "k_s1_edges")
+# a frame's first kernel: k_s1_edges opens the frame
+FIRST = ("k_s1_edges",)
 
 
 def rows(d, pat):

@@ -510,34 +510,28 @@ __global__ __launch_bounds__(SPLIT ? BLK23S : BLK23) void k_redo_stage23(BtArgs 
 }
 
 // ------------------------------------------------------------------ ByteTrack stage 1, split
-// k_stage1's work for ByteTrack (match_thresh <= 1) as two launches (three with
-// -DYTA_FUSE_DETS=0: k_s1_prep's own launch, the sequence up to DESIGN 13.10) that keep several streams
+// k_stage1's work for ByteTrack (match_thresh <= 1) as two launches that keep several streams
 // on every CU (the fused kernel holds one 1024-thread stream per CU, its 150 KiB arena, for the
 // whole latency chain of the frame).  Under load a dependent HBM round trip costs microseconds,
 // so every pass issues all of a thread's loads before using any, and hand-offs that go through
-// LDS only do not drain global stores (lds_sync):
-//   k_s1_prep  [block/stream, 256 thr, 32 KiB static LDS] detection pass and confidence split
-//              (:149-158; s1_dets_pass: items staged in LDS per pass), launched only with
-//              -DYTA_FUSE_DETS=0.  (The pool = act ++ lost with predicted boxes, :169-178, is
-//              built by the previous frame's k_finish, or by k_pool_build after a reserve.)
-//   k_s1_edges [block/stream, 512 thr, <= 62 KiB LDS] the detection pass from registers
-//              (s1_dets_fused: two rows per thread, one packed scan, lists to HBM, the high
-//              boxes handed to their list positions' threads through LDS), the grid over the
-//              high detections built in LDS from those registers, then every pool row's candidate
-//              edges, fused IoU cost (:181-183, matching.py:117, :216-220) below match_thresh:
-//              count + the first E_SLOTS edges to HBM (the grid goes to HBM too when some row
-//              has more)
+// LDS only do not drain global stores (lds_sync).  (The pool = act ++ lost with predicted boxes,
+// :169-178, is built by the previous frame's k_finish, or by k_pool_build after a reserve.  The
+// detection pass had a launch of its own, k_s1_prep, up to DESIGN 13.10; commit 15db9ac has it.)
+//   k_s1_edges [block/stream, 512 thr, <= 62 KiB LDS] the detection pass and confidence split
+//              (:149-158) from registers (s1_dets_fused: two rows per thread, one packed scan,
+//              lists to HBM, the high boxes handed to their list positions' threads through LDS),
+//              the grid over the high detections built in LDS from those registers, then every
+//              pool row's candidate edges, fused IoU cost (:181-183, matching.py:117, :216-220)
+//              below match_thresh: count + the first E_SLOTS edges to HBM (the grid goes to HBM
+//              too when some row has more)
 //   k_s1_lap   [block/stream, 256 thr] CSR of the edges in LDS (rows with more edges query the
 //              grid in HBM), lap_block with cost_limit = match_thresh (:184-186) on LDS, the
 //              assignment written out; a frame that does not fit the LDS arena is redone over
 //              global memory
 // Same results as k_stage1: edges are exactly the pairs with cost < match_thresh whatever the
 // grid's cell order, and lap_block's result does not depend on the order of a row's edges.
-constexpr int PREP_T = 256;          // k_s1_prep threads
-#ifndef YTA_PREP_CH
-#define YTA_PREP_CH 768
-#endif
-constexpr int PREP_CH = YTA_PREP_CH;  // items staged in LDS per pass of k_s1_prep
+constexpr int PREP_T = 256;          // k_pool_build threads
+constexpr int PREP_CH = 768;         // items staged in LDS per pass of s1_pool_build
 #ifndef YTA_BLKE
 #define YTA_BLKE 512
 #endif
@@ -548,20 +542,9 @@ constexpr int BLKE = YTA_BLKE;       // k_s1_edges threads
 constexpr int BLKL = YTA_BLKL;       // k_s1_lap threads
 
 struct PrepShared {
-    union {
-        struct {
-            Box box[PREP_CH];
-#if YTA_PREP_CH <= 768
-            double conf[PREP_CH];
-#endif
-            unsigned char cat[PREP_CH];
-        } d;                          // detections of the current pass
-        struct {
-            Box box[PREP_CH];
-            int slot[PREP_CH];
-            unsigned char cat[PREP_CH];
-        } t;                          // tracked tracks of the current pass
-    } u;
+    Box box[PREP_CH];                 // tracked tracks of the current pass
+    int slot[PREP_CH];
+    unsigned char cat[PREP_CH];
     int wsum[32];
 };
 
@@ -611,22 +594,22 @@ __device__ __forceinline__ void s1_pool_build(const BtArgs &a, int s, PrepShared
             [&](int, int slot) { return bt_trk_rec(a, tb, slot); },
             [&](int i, const TrkRec &r) {
                 const bool act = (r.flags & FL_ACTIVATED) != 0;
-                sh.u.t.cat[i] = act ? 1 : 2;
-                sh.u.t.slot[i] = r.slot;
-                sh.u.t.box[i] = act ? bt_pred_box(r) : xyah_mean_to_box(r.m[0], r.m[1], r.m[2], r.m[3]);
+                sh.cat[i] = act ? 1 : 2;
+                sh.slot[i] = r.slot;
+                sh.box[i] = act ? bt_pred_box(r) : xyah_mean_to_box(r.m[0], r.m[1], r.m[2], r.m[3]);
             });
         lds_sync();
         const int2 au = block_compact2<false>(
-            m, sh.wsum, [&](int i) { return (int)sh.u.t.cat[i]; },
+            m, sh.wsum, [&](int i) { return (int)sh.cat[i]; },
             [&](int i, int cat, int pos) {
                 if (cat == 1) {
                     const long long p = tb + n_act + pos;
-                    a.pool[p] = sh.u.t.slot[i];
-                    a.pool_box[p] = sh.u.t.box[i];
+                    a.pool[p] = sh.slot[i];
+                    a.pool_box[p] = sh.box[i];
                 } else {
                     const long long p = tb + n_unc + pos;
-                    a.unc[p] = sh.u.t.slot[i];
-                    a.unc_box[p] = sh.u.t.box[i];
+                    a.unc[p] = sh.slot[i];
+                    a.unc_box[p] = sh.box[i];
                 }
             });
         n_act += au.x;
@@ -663,12 +646,9 @@ __global__ __launch_bounds__(PREP_T) void k_pool_build(BtArgs a) {
 }
 
 // The detection pass of a frame (one block per stream): STrack conversions, the confidence split
-// into the order-preserving high / second lists, then the frame's counters.  It runs as its own
-// launch (k_s1_prep -> s1_dets_pass) or, with YTA_FUSE_DETS, at the top of k_s1_edges from
-// registers (s1_dets_fused); both forms share the pieces below, and write the same lists.
-#ifndef YTA_FUSE_DETS
-#define YTA_FUSE_DETS 1   // 0: k_s1_prep's own launch ahead of k_s1_edges (the A/B build)
-#endif
+// into the order-preserving high / second lists, then the frame's counters.  It runs at the top of
+// k_s1_edges from registers (s1_dets_fused), built from the pieces below.  The form with a launch
+// of its own (k_s1_prep, s1_dets_pass) lost the A/B of DESIGN 13.10 and was removed.
 
 // The stream's detection count, clamped to the capacity (ERR_DET_CAPACITY when it was not within)
 __device__ __forceinline__ int s1_det_count(const BtArgs &a, int s) {
@@ -700,77 +680,6 @@ __device__ __forceinline__ void s1_frame_counters(BtCounters *c, int nd, int n_h
     c->n_ref = 0;
 }
 
-__device__ __forceinline__ void s1_dets_pass(const BtArgs &a, int s, PrepShared &sh) {
-    BtCounters *c = a.cnt + s;
-    const long long db = (long long)s * a.MAXD;
-    const int nd = s1_det_count(a, s);
-    const double *din = a.det_in + (long long)a.det_off[s] * 6;
-    // detections, PREP_CH per pass (coalesced loads, 3 rows in flight per thread): STrack
-    // conversions (:16-18), measurement, confidence split (:149-158), boxes staged in LDS, then
-    // the order-preserving high / second lists
-    int n_high = 0, n_second = 0;
-    for (int c0 = 0; c0 < nd; c0 += PREP_CH) {
-        const int m = nd - c0 < PREP_CH ? nd - c0 : PREP_CH;
-        batched_for<3>(
-            m,
-            [&](int i) {
-                DetRow r;
-                const double *d = din + (long long)(c0 + i) * 6;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) r.v[k] = d[k];
-                return r;
-            },
-            [&](int i, const DetRow &r) {
-                double xywh[4];
-                det_xyxy_to_xywh(r.v, xywh);
-                const double conf = r.v[4];
-                sh.u.d.cat[i] = s1_det_cat(a, conf);
-                sh.u.d.box[i] = xywh_to_box(xywh);
-#if YTA_PREP_CH <= 768
-                sh.u.d.conf[i] = conf;
-#endif
-            });
-        lds_sync();
-        const int2 hs = block_compact2<false>(
-            m, sh.wsum, [&](int i) { return (int)sh.u.d.cat[i]; },
-            [&](int i, int cat, int pos) {
-                if (cat == 1) {
-                    const long long p = db + n_high + pos;
-                    a.high[p] = c0 + i;
-                    a.high_box[p] = sh.u.d.box[i];
-#if YTA_PREP_CH <= 768
-                    a.high_score[p] = sh.u.d.conf[i];
-#else
-                    a.high_score[p] = din[(long long)(c0 + i) * 6 + 4];   // L2-resident
-#endif
-                } else {
-                    const long long p = db + n_second + pos;
-                    a.second[p] = c0 + i;
-                    a.second_box[p] = sh.u.d.box[i];
-                }
-            });
-        n_high += hs.x;
-        n_second += hs.y;
-        lds_sync();   // the staging area is reused
-    }
-    YTA_STAMP(1);
-    s1_frame_counters(c, nd, n_high, n_second);
-}
-
-// NT: PREP_T, or 1024 with few streams (split23: one block per stream takes the lists)
-template <int NT>
-__global__ __launch_bounds__(NT) void k_s1_prep(BtArgs a) {
-    __shared__ PrepShared sh;
-    const int s = blockIdx.x;
-    if (stream_skipped(a, s)) return;
-    YTA_STAMP_BASE(60);
-    YTA_STAMP(0);
-    YTA_BLK(0, 0);
-    s1_dets_pass(a, s, sh);
-    YTA_STAMP(3);
-    YTA_BLK(0, 1);
-}
-
 // Exclusive block scans of two values at once (one barrier pair).  wsum: 32 ints.
 __device__ __forceinline__ void block_exclusive_scan_pair(int x, int y, int *wsum, int &ex, int &ey,
                                                           int &tx, int &ty) {
@@ -793,7 +702,7 @@ __device__ __forceinline__ void block_exclusive_scan_pair(int x, int y, int *wsu
 // The detection pass inside k_s1_edges: thread t takes rows c0 + t and c0 + t + blockDim of each
 // chunk of 2 blockDim rows into registers, and one packed scan per chunk (high | second << 16, the
 // chunk's two halves side by side) gives every row its place in detection order - the lists
-// block_compact2 writes in s1_dets_pass.  One chunk (nd <= 2 blockDim) is the shape the
+// k_stage1's block_compact2 writes.  One chunk (nd <= 2 blockDim) is the shape the
 // register-held grid build needs: then `hand` (hand_cap bytes of LDS; 5 arrays of n_high doubles)
 // gets the high boxes and scores by list position, for the thread that owns position j (handed;
 // false when the pass took several chunks or the area is too small).  Returns n_high; the caller
@@ -944,20 +853,13 @@ __device__ __forceinline__ void s1_edges_body(const BtArgs &a, int s, int nc, in
 // order-free).  Queues hold WQ_CAP entries; a larger candidate total is listed and scored in
 // windows.  Big items (larger than 4 x the mean box) are visited per lane, as grid_query does.
 constexpr int WQ_CAP = 384;
-#ifndef YTA_S1_P1
-#define YTA_S1_P1 1   // k_s1_edges' queue passes: two chunks per trip, branch-free tests (round 6)
-#endif
-#ifndef YTA_S1_SOA
-#define YTA_S1_SOA 1   // k_s1_edges' LDS grid keeps its boxes as four arrays (GridView::sx)
-#endif
+// The LDS grid keeps its boxes as four arrays (GridView::sx): conflict-free wave reads.  The
+// array-of-boxes layout and the one-chunk, short-circuit queue passes
+// lost their A/Bs and were removed; commit 15db9ac has them.
 __device__ __forceinline__ Box s1_box(const GridView &gv, int k) {
-#if YTA_S1_SOA
     const double *x = gv.sx;
     const int n = gv.sn;
     return Box{x[k], x[n + k], x[2 * n + k], x[3 * n + k]};
-#else
-    return gv.boxes[k];
-#endif
 }
 struct EdgeWaveQ {
     unsigned q[WQ_CAP];   // lane << 24 | grid position
@@ -1016,7 +918,6 @@ __device__ __forceinline__ void s1_edges_rows_wave(const BtArgs &a, int s, int n
             // pass 1: keep the intersecting candidates (compacted in place: a survivor's new index
             // is at most its old one, and a chunk is read before any of it is overwritten)
             int ns = 0;
-#if YTA_S1_P1
             // Two chunks of 64 per trip, every load of both issued before any test, and the test
             // branch-free: a queued row box has x2 > x1 and y2 > y1 (grid_scan_window lists
             // nothing otherwise, NaN included) and a binned box is usable, so intersects()
@@ -1043,25 +944,12 @@ __device__ __forceinline__ void s1_edges_rows_wave(const BtArgs &a, int s, int n
                 if (hb) wq.q[ns + na + __popcll(bb & lt)] = eb;
                 ns += na + __popcll(bb);
             }
-#else
-            for (int k0 = 0; k0 < n; k0 += WAVE) {   // wave-uniform trip count
-                const int k = k0 + lane;
-                const unsigned ent = k < n ? wq.q[k] : 0u;
-                const int r = (int)(ent >> 24), pos = (int)(ent & 0xFFFFFFu);
-                const Box tb_{bperm_f64(rb.x1, r), bperm_f64(rb.y1, r), bperm_f64(rb.x2, r),
-                              bperm_f64(rb.y2, r)};
-                const bool hit = k < n && intersects(tb_, s1_box(gv, pos));
-                const unsigned long long bal = __ballot(hit);
-                if (hit) wq.q[ns + __popcll(bal & ((1ull << lane) - 1ull))] = ent;
-                ns += __popcll(bal);
-            }
-#endif
             __builtin_amdgcn_wave_barrier();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             // pass 2: score the survivors (full lanes for the float64 IoU)
             for (int k0 = 0; k0 < ns; k0 += WAVE) {
                 const int k = k0 + lane;
-#if YTA_S1_P1   // every operand's load issued before the row box arrives and before any branch
+                // every operand's load issued before the row box arrives and before any branch
                 const unsigned ent = wq.q[k < ns ? k : 0];
                 const int r = (int)(ent >> 24), pos = (int)(ent & 0xFFFFFFu);
                 const Box cb = s1_box(gv, pos);
@@ -1073,18 +961,6 @@ __device__ __forceinline__ void s1_edges_rows_wave(const BtArgs &a, int s, int n
                 const double dist = 1 - iou(tb_, cb);                   // matching.py:117
                 const double cost = 1 - (1 - dist) * wj;                // matching.py:216-220
                 if (!(cost < thresh)) continue;
-#else
-                const unsigned ent = k < ns ? wq.q[k] : 0u;
-                const int r = (int)(ent >> 24), pos = (int)(ent & 0xFFFFFFu);
-                const Box tb_{bperm_f64(rb.x1, r), bperm_f64(rb.y1, r), bperm_f64(rb.x2, r),
-                              bperm_f64(rb.y2, r)};
-                if (k >= ns) continue;
-                const Box cb = s1_box(gv, pos);
-                const double dist = 1 - iou(tb_, cb);                   // matching.py:117
-                const double cost = 1 - (1 - dist) * gv.w[pos];         // matching.py:216-220
-                if (!(cost < thresh)) continue;
-                const int j = gv.ids[pos];
-#endif
                 const int c = atomicAdd(&wq.cnt[r], 1);
                 if (c < E_SLOTS) {
                     a.e_col[c * SC + tb + base + r] = j;
@@ -1187,8 +1063,7 @@ __global__ __launch_bounds__(NT, NT == BLKE ? 4 : 1) void k_s1_edges(BtArgs a) {
     // grid build reads them three times)
     Box hb0{0.0, 0.0, 0.0, 0.0}, hb1{0.0, 0.0, 0.0, 0.0};
     double hw0 = 0.0, hw1 = 0.0;
-#if YTA_FUSE_DETS
-    // The frame's detection pass first (k_s1_prep's work): the lists go to HBM for the later
+    // The frame's detection pass first: the lists go to HBM for the later
     // kernels, and the high boxes reach their list positions' threads through the arena, which is
     // free until the grid is built.  The area overlaps the grid arrays: it is dead (second
     // lds_sync) before grid_build or cdeg write them.
@@ -1210,10 +1085,6 @@ __global__ __launch_bounds__(NT, NT == BLKE ? 4 : 1) void k_s1_edges(BtArgs a) {
         lds_sync();
     } else {
         block_sync();   // the lists this block stored are read back below
-#else
-    const int nc = c->n_high, nr = c->n_pool;
-    {
-#endif
         // every box load in flight at once
         if (t < nc) {
             hb0 = a.high_box[db + t];
@@ -1225,7 +1096,7 @@ __global__ __launch_bounds__(NT, NT == BLKE ? 4 : 1) void k_s1_edges(BtArgs a) {
         }
     }
     // Both grid paths below read high_box / high_score from global memory (big items, the HBM
-    // grid's build): with the fused pass these are this block's own stores, and every such read
+    // grid's build): these are this block's own stores, and every such read
     // follows a block_sync (the HBM path's own, grid_build's on the LDS path).
     int rn[4] = {0, 0, 0, 0}, rc[4] = {-1, -1, -1, -1};   // rows t + b * nt (s1_single_edges)
     if (nc > 2 * nt || s1_grid_bytes(nc) + 4LL * nc > (long long)a.lds_bytes_e) {   // HBM grid
@@ -1248,13 +1119,9 @@ __global__ __launch_bounds__(NT, NT == BLKE ? 4 : 1) void k_s1_edges(BtArgs a) {
     gv.hdr = nullptr;
     gv.cell_start = ar.alloc<int>(grid_cells_for(nc) + 1);
     gv.ids = ar.alloc<int>(nc);
-#if YTA_S1_SOA
     gv.boxes = nullptr;   // the boxes as four arrays (GridView::sx): conflict-free wave reads
     gv.sx = ar.alloc<double>(4LL * nc);
     gv.sn = nc;
-#else
-    gv.boxes = ar.alloc<Box>(nc);
-#endif
     gv.w = ar.alloc<double>(nc);
     gv.big = ar.alloc<int>(nc);
     int *cdeg = ar.alloc<int>(nc);
@@ -1881,9 +1748,8 @@ __device__ __forceinline__ void take_detection(const BtArgs &a, KfState &st, Tra
 // pieces of a record (full-line reads and writes); each thread then runs the Kalman step of one
 // track out of LDS.  LDS row: pieces 0-3 the mean, 4-6 the meta, 7-14 the covariance (record
 // pieces 0-6 and 8-15: the padding piece 7 is skipped).
-#ifndef YTA_APPLY_XCD
-#define YTA_APPLY_XCD 1   // k_apply: the blocks of a stream share an XCD (xcd_stream_blocks); 0: launch order
-#endif
+// The blocks of a stream share an XCD (xcd_stream_blocks); plain launch order lost the A/B of
+// DESIGN 13.9 and was removed (commit 558961d has both).
 constexpr int APPLY_T = 128;              // tracks (= threads) per block
 constexpr int REC_PIECES = 15;            // 16-B pieces of a record that carry data
 constexpr int L_META = 8, L_COV = 14;     // doubles: meta / covariance in an LDS row
@@ -1898,9 +1764,7 @@ __global__ __launch_bounds__(APPLY_T) void k_apply(BtArgs a) {
     __shared__ int s_wmask[APPLY_T];      // bit 0: write the Kalman record, bit 1: write the meta
     // logical (stream, block) of this workgroup: a stream's blocks on one XCD (common.hpp)
     int s = blockIdx.y, bx = blockIdx.x;
-#if YTA_APPLY_XCD
     xcd_stream_blocks(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x, gridDim.y, s, bx);
-#endif
     const int t = threadIdx.x;
     if (stream_skipped(a, s)) return;
     BtCounters *c = a.cnt + s;
@@ -2345,7 +2209,7 @@ __device__ __forceinline__ void finish_body(const BtArgs &a, int s, unsigned *bi
             return V == VAR_BOTSORT ? xywh_to_box(v.m) : xyah_mean_to_box(v.m[0], v.m[1], v.m[2], v.m[3]);
         };
         // a lost' track's box is the one stage 1 used, pool_box at its pool position: ByteTrack's
-        // lazily predicted mean (k_s1_prep / the last k_finish), BoT-SORT's predicted and warped
+        // lazily predicted mean (the last k_finish / k_pool_build), BoT-SORT's predicted and warped
         // mean (stage1_lists: the same x + v and kron(I4, R) x + t operations as k_apply's
         // kf_predict / kf_predict_x and kf_gmc on the record, so the same bits, and no record read)
         // each entry's pool position kept beside its float box (one global round trip, not two,
@@ -2439,7 +2303,7 @@ __device__ __forceinline__ void finish_body(const BtArgs &a, int s, unsigned *bi
     // over tracked' (one scan of packed counts), output rows, free slots.  ByteTrack (split stage
     // 1): the next frame's stage-1 pool too (NP): its head = the output slots with their predicted
     // boxes (the output pass holds their means), the unconfirmed = the kept non-activated entries
-    // (births), the tail = the final lost list, lazily predicted - what k_s1_prep gathered from the
+    // (births), the tail = the final lost list, lazily predicted - what used to be gathered from the
     // records at the start of the next frame (s1_pool_build), from rows this kernel already reads.
     constexpr bool NPV = V == VAR_BYTETRACK;
     const bool NP = NPV && a.match_thresh <= 1.0;
@@ -2499,7 +2363,7 @@ __device__ __forceinline__ void finish_body(const BtArgs &a, int s, unsigned *bi
         });
     // free slots below start in cyclic order from the slot after this frame's last birth: births
     // then take ascending slots across frames, so the tracked list (survivors in order, births
-    // appended) stays sorted by slot up to a rotation, and the record gathers of k_s1_prep /
+    // appended) stays sorted by slot up to a rotation, and the record gathers of k_pool_build /
     // k_apply / k_finish walk memory in (gapped) ascending order instead of at random.  Read here,
     // so that only LDS is handed over between the output rows and the free-list pass.
     if (t == 0) sh.cur = n_births > 0 ? (a.free_list[tb + n_births - 1] + 1) % a.CAP : c->slot_cursor;
@@ -2667,7 +2531,6 @@ __global__ __launch_bounds__(NT) void k_redo_finish(BtArgs a) {
     redo_drain(a, [&](int s, Arena &ag) { finish_body<V>(a, s, bits, ag, sh, false); });
 }
 
-// Rebuild the free-slot list of every stream from its tracked + lost lists (after a reserve).
 // Host-buffer update: every stream's output rows (a.out + s * CAP * 8) packed back to back at the
 // prefix offsets, so one copy returns them.  Block per stream, 16-B pieces.  Rows at or past
 // `limit` (the destination's capacity) are not written: the host compares the offsets with it.
@@ -2823,11 +2686,9 @@ __global__ __launch_bounds__(OFFS_T) void k_out_offsets_scan(const BtCounters *c
 // command's release to flush) the completions were prompt but the frame's first kernel ran
 // 1.7 ms beside them.  Fewer blocks keep fewer host stores in flight: 2048 streams, 3 frames in
 // flight, page-locked buffers, same box: 128 blocks 574 k calls/s, 64 620 k, 48 700 k, 32 750 k,
-// 24 743 k, 16 717 k, 8 605 k; 32 blocks with plain stores 563 k.
+// 24 743 k, 16 717 k, 8 605 k; 32 blocks with plain stores 563 k.  (The plain, nontemporal and
+// sc0 sc1 nt stores lost that A/B, DESIGN 13.5, and were removed; commit 15db9ac has them.)
 constexpr int ROWS_H_BLOCKS = 32;
-#ifndef YTA_D2H_STORE
-#define YTA_D2H_STORE 2   // k_rows_to_host's stores: 0 plain, 1 nontemporal, 2 sc0 sc1, 3 sc0 sc1 nt
-#endif
 __global__ __launch_bounds__(1024) void k_copy_ints(const int *src, int *dst, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
 }
@@ -2839,20 +2700,10 @@ __global__ __launch_bounds__(256) void k_rows_to_host(const double *src, const i
     const int4 *s4 = reinterpret_cast<const int4 *>(src);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) {
-#if YTA_D2H_STORE >= 1
         typedef int v4i __attribute__((ext_vector_type(4)));
         const v4i v = reinterpret_cast<const v4i *>(s4)[i];
         v4i *d = reinterpret_cast<v4i *>(dst) + i;
-#if YTA_D2H_STORE == 1
-        __builtin_nontemporal_store(v, d);
-#elif YTA_D2H_STORE == 2
         asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(d), "v"(v) : "memory");
-#else
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(d), "v"(v) : "memory");
-#endif
-#else
-        dst[i] = s4[i];
-#endif
     }
 }
 
@@ -2868,6 +2719,7 @@ __global__ __launch_bounds__(256) void k_cnt_to_host(const BtCounters *cnt, int 
         dst[i] = src[i];
 }
 
+// Rebuild the free-slot list of every stream from its tracked + lost lists (after a reserve).
 __global__ __launch_bounds__(BLKF) void k_rebuild_free(BtArgs a) {
     __shared__ int wsum[32];
     extern __shared__ __attribute__((aligned(16))) unsigned int live[];
@@ -3055,7 +2907,7 @@ struct yta_bytetrack {
         double *d_pack = nullptr, *h_pack = nullptr; // packed output rows
         long long pack_cap = 0;
         int *d_pack_off = nullptr, *h_pack_off = nullptr;   // S + 1 row offsets
-        BtCounters *d_cnt = nullptr, *h_cnt = nullptr;      // counters after this frame (d_cnt unused)
+        BtCounters *h_cnt = nullptr;                 // counters after this frame
         BtCounters *m_cnt = nullptr;                 // h_cnt as the device sees it (mapped)
         int *m_pack_off = nullptr;                   // h_pack_off as the device sees it
         double *m_pack = nullptr;                    // h_pack as the device sees it
@@ -3202,6 +3054,41 @@ inline size_t stage_chunk(size_t bytes) {
     const int n = bytes >= (16u << 20) ? STAGE_CHUNKS : 1;
     return ((bytes + n - 1) / n + 63) & ~(size_t)63;
 }
+// Pageable `src` to the device buffer `dev` through its page-locked twin `pinned`, on `st`: chunk
+// k's DMA overlaps chunk k+1's host copy.
+int stage_h2d(yta_bytetrack *e, void *dev, void *pinned, const void *src, size_t bytes,
+              hipStream_t st) {
+    const size_t ch = stage_chunk(bytes);
+    for (size_t o = 0; o < bytes; o += ch) {
+        const size_t n = std::min(ch, bytes - o);
+        par_copy(e, (char *)pinned + o, (const char *)src + o, n);
+        YTA_HIP(hipMemcpyAsync((char *)dev + o, (char *)pinned + o, n, hipMemcpyHostToDevice, st));
+    }
+    return YTA_OK;
+}
+
+// A device buffer *d and its page-locked twin *h (host_flags) of *cap elements of elem_bytes:
+// when `need` outgrows them, both are freed (contents dropped) and allocated anew with new_cap
+// elements, the caller's growth rule.
+template <typename T>
+int grow_pair(T **d, T **h, long long *cap, long long need, size_t elem_bytes, long long new_cap,
+              unsigned host_flags = hipHostMallocDefault) {
+    if (need <= *cap) return YTA_OK;
+    if (*d) (void)hipFree(*d);
+    if (*h) (void)hipHostFree(*h);
+    *d = *h = nullptr;
+    *cap = 0;
+    YTA_HIP(hipMalloc((void **)d, elem_bytes * new_cap));
+    YTA_HIP(hipHostMalloc((void **)h, elem_bytes * new_cap, host_flags));
+    *cap = new_cap;
+    return YTA_OK;
+}
+
+// Host milliseconds from t0 to t1 (now), for the pstat accumulators
+using HostClock = std::chrono::steady_clock;
+inline double ms_since(HostClock::time_point t0, HostClock::time_point t1 = HostClock::now()) {
+    return std::chrono::duration<double, std::milli>(t1 - t0).count();
+}
 
 template <typename T>
 int dalloc(yta_bytetrack *e, T **p, long long n) {
@@ -3316,7 +3203,7 @@ int bt_alloc(yta_bytetrack *e) {
         DALLOC(a.e_col, E_SLOTS * S * CAP);
         DALLOC(a.e_cost, E_SLOTS * S * CAP);
     }
-    if (e->variant == VAR_BYTETRACK) {   // stage 1 as k_s1_prep / k_s1_edges / k_s1_lap
+    if (e->variant == VAR_BYTETRACK) {   // stage 1 as k_s1_edges / k_s1_lap
         a.ws_stride = std::max(a.ws_stride, s1_lap_arena_bytes(CAP, MAXD, CAP * MAXD));
         DALLOC(a.g_cell, S * (GRID_MAX_CELLS + 1));
         DALLOC(a.g_ids, S * MAXD);
@@ -3389,17 +3276,16 @@ int set_lds_limits(size_t bytes) {
     return YTA_OK;
 }
 
-// One frame of every stream: 5 launches (ByteTrack; 6 with -DYTA_FUSE_DETS=0, else phase s1_prep
-// is an empty interval and s1_edges holds the detection pass), 4 + k_feat and k_ema (BoT-SORT, fused stage
+// One frame of every stream: 5 launches (ByteTrack), 4 + k_feat and k_ema (BoT-SORT, fused stage
 // 1); with more streams than pooled fallback arenas each association kernel is followed by its
-// redo kernel (ws_slots blocks that return at once unless a stream fell back).  Profiling marks bracket the phases s1_prep / s1_edges / s1_lap (BoT-SORT: k_feat + k_stage1,
-// empty, empty), stage23, apply (k_apply + k_ema), finish.
-// a launch of more association blocks than pooled arenas queues its fallbacks for a redo kernel
-// (redo_in_place on the device)
-#ifndef YTA_REDO_LAUNCH
-#define YTA_REDO_LAUNCH 1   // 0: an A/B build without the redo launches (unsafe if a stream falls back)
-#endif
-static bool redo_launch(const BtArgs &a, int blocks) { return YTA_REDO_LAUNCH && blocks > a.ws_slots; }
+// redo kernel (ws_slots blocks that return at once unless a stream fell back).  Profiling marks
+// bracket the phases s1_prep / s1_edges / s1_lap (ByteTrack: s1_prep is an empty interval since
+// k_s1_edges took the detection pass in; BoT-SORT: k_feat + k_stage1, empty,
+// empty), stage23, apply (k_apply + k_ema), finish.
+// A launch of more association blocks than pooled arenas queues its fallbacks for a redo kernel
+// (redo_in_place on the device).  (A build without the redo launches was measured in DESIGN 13.4;
+// it loses a stream's frame whenever one falls back, and is gone.)
+static bool redo_launch(const BtArgs &a, int blocks) { return blocks > a.ws_slots; }
 
 template <int V>
 int launch_frame(yta_bytetrack *e) {
@@ -3416,14 +3302,7 @@ int launch_frame(yta_bytetrack *e) {
         YTA_HIP(hipGetLastError());
     }
     if (V == VAR_BYTETRACK && a.match_thresh <= 1.0) {   // grid-exact candidates (assoc.hpp)
-#if !YTA_FUSE_DETS   // else k_s1_edges opens with the detection pass: phase s1_prep is empty
-        if (e->split23)
-            hipLaunchKernelGGL(k_s1_prep<1024>, dim3(a.S), dim3(1024), 0, e->stream, a);
-        else
-            hipLaunchKernelGGL(k_s1_prep<PREP_T>, dim3(a.S), dim3(PREP_T), 0, e->stream, a);
-        YTA_HIP(hipGetLastError());
-#endif
-        MARK();
+        MARK();   // k_s1_edges opens with the detection pass: phase s1_prep is empty
         if (e->split23)
             hipLaunchKernelGGL(k_s1_edges<1024>, dim3(a.S), dim3(1024), a.lds_bytes_e, e->stream, a);
         else
@@ -3436,8 +3315,8 @@ int launch_frame(yta_bytetrack *e) {
                 hipLaunchKernelGGL(k_redo_s1_lap<1024>, dim3(a.ws_slots), dim3(1024), 0, e->stream, a);
         } else {
             hipLaunchKernelGGL(k_s1_lap<BLKL>, dim3(a.S), dim3(BLKL), a.lds_bytes_l, e->stream, a);
-            if (YTA_REDO_LAUNCH)
-                hipLaunchKernelGGL(k_redo_s1_lap<BLKL>, dim3(a.ws_slots), dim3(BLKL), 0, e->stream, a);
+            // the many-stream kernel always queues its fallbacks (k_s1_lap)
+            hipLaunchKernelGGL(k_redo_s1_lap<BLKL>, dim3(a.ws_slots), dim3(BLKL), 0, e->stream, a);
         }
     } else if (bs) {   // split stage 1 (k_bs_*): few streams
         hipLaunchKernelGGL(k_bs_prep, dim3(a.S + a.S * feat_blocks(a.MAXD, BS_PREP_T)),
@@ -3625,6 +3504,14 @@ int reserve(yta_bytetrack *e, int cap, int maxd) {
     return YTA_OK;
 }
 
+// Room for need_c tracks and need_d detections a stream: whichever capacity falls short grows
+// geometrically (at least doubling), keeping all state.
+int grow_for(yta_bytetrack *e, int need_c, int need_d) {
+    if (need_c <= e->CAP && need_d <= e->MAXD) return YTA_OK;
+    return reserve(e, need_c > e->CAP ? std::max(need_c, 2 * e->CAP) : e->CAP,
+                   need_d > e->MAXD ? std::max(need_d, 2 * e->MAXD) : e->MAXD);
+}
+
 int check_errors(yta_bytetrack *e) {
     for (int s = 0; s < e->S; ++s) {
         const int err = e->h_cnt[s].err;
@@ -3640,6 +3527,29 @@ int check_errors(yta_bytetrack *e) {
                        : YTA_ERR_HIP;
         }
     }
+    return YTA_OK;
+}
+
+// A host-buffer frame once its counters are on the host (h_cnt): next_id handed back (the device
+// counters have advanced: even when an error follows), the streams' error flags, then
+// out_offsets as the prefix sums of the output counts, *rows their total.
+int finish_counts(yta_bytetrack *e, long long *next_id, const double *out, int out_capacity,
+                  int *out_offsets, long long *rows) {
+    const int S = e->S;
+    if (next_id)
+        for (int s = 0; s < S; ++s) next_id[s] = e->h_cnt[s].next_id;
+    const int rc = check_errors(e);
+    if (rc) return rc;
+    long long r = 0;
+    out_offsets[0] = 0;
+    for (int s = 0; s < S; ++s) {
+        r += e->h_cnt[s].n_out;
+        out_offsets[s + 1] = (int)r;
+    }
+    YTA_CHECK(r <= out_capacity, YTA_ERR_CAPACITY, "output needs %lld rows > capacity %d", r,
+              out_capacity);
+    YTA_CHECK(r == 0 || out, YTA_ERR_INVALID, "null out");
+    *rows = r;
     return YTA_OK;
 }
 
@@ -3730,20 +3640,16 @@ constexpr long long SMALL_PACK_BYTES = 1LL << 20;   // single-round-trip host up
 // slowly growing output does not reallocate every frame) and the S + 1 offsets.
 int ensure_pack(yta_bytetrack *e, long long rows) {
     if (rows <= e->pack_cap && e->d_pack_off) return YTA_OK;
-    if (e->d_pack) (void)hipFree(e->d_pack);
-    if (e->h_pack) (void)hipHostFree(e->h_pack);
     if (e->d_pack_off) (void)hipFree(e->d_pack_off);
     if (e->h_pack_off) (void)hipHostFree(e->h_pack_off);
-    e->d_pack = e->h_pack = nullptr;
     e->d_pack_off = e->h_pack_off = nullptr;
-    e->pack_cap = 0;
-    const long long cap = std::max<long long>(2 * rows, 1024);
+    // the first call allocates whatever `rows` is (the offsets travel with the row buffers)
+    const int rc = grow_pair(&e->d_pack, &e->h_pack, &e->pack_cap, std::max(rows, 1LL),
+                             sizeof(double) * 8, std::max<long long>(2 * rows, 1024));
+    if (rc) return rc;
     const int S = e->S;
-    YTA_HIP(hipMalloc((void **)&e->d_pack, sizeof(double) * 8 * cap));
-    YTA_HIP(hipHostMalloc((void **)&e->h_pack, sizeof(double) * 8 * cap, hipHostMallocDefault));
     YTA_HIP(hipMalloc((void **)&e->d_pack_off, sizeof(int) * (S + 1)));
     YTA_HIP(hipHostMalloc((void **)&e->h_pack_off, sizeof(int) * (S + 1), hipHostMallocDefault));
-    e->pack_cap = cap;
     return YTA_OK;
 }
 
@@ -3751,28 +3657,15 @@ int ensure_pack(yta_bytetrack *e, long long rows) {
 // page-locked staging when the caller's buffer is pageable; enqueued on `st`.
 int stage_f32(yta_bytetrack *e, const float *src, long long n, float **dbuf, float **hbuf,
               long long *cap, hipStream_t st) {
-    if (n > *cap) {
-        if (*dbuf) (void)hipFree(*dbuf);
-        if (*hbuf) (void)hipHostFree(*hbuf);
-        *dbuf = *hbuf = nullptr;
-        *cap = 0;
-        const long long c = std::max<long long>(n + n / 8, 6144);
-        YTA_HIP(hipMalloc((void **)dbuf, sizeof(float) * c));
-        YTA_HIP(hipHostMalloc((void **)hbuf, sizeof(float) * c, hipHostMallocDefault));
-        *cap = c;
-    }
+    const int rc = grow_pair(dbuf, hbuf, cap, n, sizeof(float),
+                             std::max<long long>(n + n / 8, 6144));
+    if (rc) return rc;
     const size_t bytes = sizeof(float) * n;
     if (host_pinned(src, bytes)) {
         YTA_HIP(hipMemcpyAsync(*dbuf, src, bytes, hipMemcpyHostToDevice, st));
         return YTA_OK;
     }
-    const size_t ch = stage_chunk(bytes);
-    for (size_t o = 0; o < bytes; o += ch) {
-        const size_t m = std::min(ch, bytes - o);
-        par_copy(e, (char *)*hbuf + o, (const char *)src + o, m);
-        YTA_HIP(hipMemcpyAsync((char *)*dbuf + o, (char *)*hbuf + o, m, hipMemcpyHostToDevice, st));
-    }
-    return YTA_OK;
+    return stage_h2d(e, *dbuf, *hbuf, src, bytes, st);
 }
 
 int widen_f32(const float *src, double *dst, long long n, hipStream_t st) {
@@ -3857,11 +3750,8 @@ int update_host(yta_bytetrack *e, const double *dets, const int *det_offsets, co
     // det_offsets[S] rows always suffice; checked before anything moves (the frame is not consumed)
     YTA_CHECK(out_capacity >= det_offsets[S], YTA_ERR_CAPACITY,
               "out holds %d rows, the call needs det_offsets[S] = %d", out_capacity, det_offsets[S]);
-    if (need_d > e->MAXD || need_c > e->CAP) {   // grow geometrically, keeping all state
-        const int rc = reserve(e, need_c > e->CAP ? std::max(need_c, 2 * e->CAP) : e->CAP,
-                               need_d > e->MAXD ? std::max(need_d, 2 * e->MAXD) : e->MAXD);
-        if (rc) return rc;
-    }
+    int rc = grow_for(e, need_c, need_d);
+    if (rc) return rc;
     if (e->variant == VAR_BOTSORT) {   // this frame's camera warps (staged after any reserve)
         e->a.warp = e->d_warp_id;
         if (warps && !identity_warps(warps, S)) {
@@ -3874,48 +3764,23 @@ int update_host(yta_bytetrack *e, const double *dets, const int *det_offsets, co
     }
     const long long total = det_offsets[S];
     YTA_CHECK(total == 0 || dets || dets32, YTA_ERR_INVALID, "null dets");
-    if (total > e->d_det_cap) {
-        if (e->d_det_in) (void)hipFree(e->d_det_in);
-        if (e->h_dets) (void)hipHostFree(e->h_dets);
-        e->d_det_in = nullptr;
-        e->h_dets = nullptr;
-        e->d_det_cap = 0;
-        const long long cap = std::max<long long>(2 * total, 1024);
-        YTA_HIP(hipMalloc((void **)&e->d_det_in, sizeof(double) * 6 * cap));
-        YTA_HIP(hipHostMalloc((void **)&e->h_dets, sizeof(double) * 6 * cap, hipHostMallocDefault));
-        e->d_det_cap = cap;
-    }
+    const long long twice = std::max<long long>(2 * total, 1024);   // staging growth rule
+    rc = grow_pair(&e->d_det_in, &e->h_dets, &e->d_det_cap, total, sizeof(double) * 6, twice);
+    if (rc) return rc;
     if (total && dets32) {   // float32 rows: half the bytes over the link, widened on the device
-        int src = stage_f32(e, dets32, 6 * total, &e->d_det32, &e->h_det32, &e->det32_cap,
-                            e->stream);
-        if (!src) src = widen_f32(e->d_det32, e->d_det_in, 6 * total, e->stream);
-        if (src) return src;
+        rc = stage_f32(e, dets32, 6 * total, &e->d_det32, &e->h_det32, &e->det32_cap, e->stream);
+        if (!rc) rc = widen_f32(e->d_det32, e->d_det_in, 6 * total, e->stream);
     } else if (total && host_pinned(dets, sizeof(double) * 6 * total)) {   // straight from the caller
         YTA_HIP(hipMemcpyAsync(e->d_det_in, dets, sizeof(double) * 6 * total,
                                hipMemcpyHostToDevice, e->stream));
-    } else if (total) {   // chunk k's DMA overlaps chunk k+1's host copy
-        const size_t bytes = sizeof(double) * 6 * total, ch = stage_chunk(bytes);
-        for (size_t o = 0; o < bytes; o += ch) {
-            const size_t n = std::min(ch, bytes - o);
-            par_copy(e, (char *)e->h_dets + o, (const char *)dets + o, n);
-            YTA_HIP(hipMemcpyAsync((char *)e->d_det_in + o, (char *)e->h_dets + o, n,
-                                   hipMemcpyHostToDevice, e->stream));
-        }
+    } else if (total) {
+        rc = stage_h2d(e, e->d_det_in, e->h_dets, dets, sizeof(double) * 6 * total, e->stream);
     }
+    if (rc) return rc;
     const int D = e->a.D;
     if (D > 0 && total) {
-        if (total > e->feat_cap) {
-            if (e->d_feat_in) (void)hipFree(e->d_feat_in);
-            if (e->h_feat) (void)hipHostFree(e->h_feat);
-            e->d_feat_in = nullptr;
-            e->h_feat = nullptr;
-            e->feat_cap = 0;
-            const long long cap = std::max<long long>(2 * total, 1024);
-            YTA_HIP(hipMalloc((void **)&e->d_feat_in, sizeof(float) * D * cap));
-            YTA_HIP(hipHostMalloc((void **)&e->h_feat, sizeof(float) * D * cap,
-                                  hipHostMallocDefault));
-            e->feat_cap = cap;
-        }
+        rc = grow_pair(&e->d_feat_in, &e->h_feat, &e->feat_cap, total, sizeof(float) * D, twice);
+        if (rc) return rc;
         long long k = 0;   // next high row of feats
         for (long long r = 0; r < total; ++r)
             if (dets[r * 6 + 4] > e->a.track_thresh) {
@@ -3948,7 +3813,6 @@ int update_host(yta_bytetrack *e, const double *dets, const int *det_offsets, co
     // at device-computed offsets and copied back with the counters, one round trip per frame
     const long long worst = (long long)S * e->CAP;
     const bool small = worst * 64 <= SMALL_PACK_BYTES;
-    int rc = YTA_OK;
     if (small) {
         rc = ensure_pack(e, worst);
         if (rc) return rc;
@@ -3993,40 +3857,18 @@ int update_host(yta_bytetrack *e, const double *dets, const int *det_offsets, co
     e->a.active = nullptr;
     e->a.cnt_mirror = nullptr;
     if (rc) return rc;
+    long long rows = 0;
     if (small) {
         YTA_HIP(host_wait(e->stream));
         if (one) memcpy(e->h_cnt, e->h_pack + worst * 8, sizeof(BtCounters));
-        if (next_id)   // the device counters have advanced: hand them back even on an error below
-            for (int q = 0; q < S; ++q) next_id[q] = e->h_cnt[q].next_id;
-        rc = check_errors(e);
+        rc = finish_counts(e, next_id, out, out_capacity, out_offsets, &rows);
         if (rc) return rc;
-        long long rows = 0;
-        out_offsets[0] = 0;
-        for (int q = 0; q < S; ++q) {
-            rows += e->h_cnt[q].n_out;
-            out_offsets[q + 1] = (int)rows;
-        }
-        YTA_CHECK(rows <= out_capacity, YTA_ERR_CAPACITY, "output needs %lld rows > capacity %d",
-                  rows, out_capacity);
-        YTA_CHECK(rows == 0 || out, YTA_ERR_INVALID, "null out");
         if (rows > 0) memcpy(out, e->h_pack, sizeof(double) * 8 * rows);
         return YTA_OK;
     }
     rc = read_counters(e);
+    if (!rc) rc = finish_counts(e, next_id, out, out_capacity, out_offsets, &rows);
     if (rc) return rc;
-    if (next_id)   // the device counters have advanced: hand them back even on an error below
-        for (int s = 0; s < S; ++s) next_id[s] = e->h_cnt[s].next_id;
-    rc = check_errors(e);
-    if (rc) return rc;
-    long long rows = 0;
-    out_offsets[0] = 0;
-    for (int s = 0; s < S; ++s) {
-        rows += e->h_cnt[s].n_out;
-        out_offsets[s + 1] = (int)rows;
-    }
-    YTA_CHECK(rows <= out_capacity, YTA_ERR_CAPACITY, "output needs %lld rows > capacity %d", rows,
-              out_capacity);
-    YTA_CHECK(rows == 0 || out, YTA_ERR_INVALID, "null out");
     if (rows > 0) {   // pack on the device, one copy back through pinned staging
         rc = ensure_pack(e, rows);
         if (rc) return rc;
@@ -4129,13 +3971,14 @@ int update_host_subset(yta_bytetrack *e, int n, const int *ids, const double *de
 
 // ---- pipelined host-buffer update --------------------------------------------------------------
 // Frame f's detections go host -> device on s_in while frame f-1's kernels run on the compute
-// stream and frame f-2's rows come back on s_out (PIPE_DEPTH frames in flight) (both PCIe directions and the kernels at once).
+// stream and frame f-2's rows come back on s_out (PIPE_DEPTH frames in flight: both PCIe
+// directions and the kernels at once).
 // The compute stream snapshots every frame's rows (k_pack_out into the slot) and counters before
 // the next frame's kernels can touch them, so the copy-out of frame f never races frame f+1.
 void pipe_free(yta_bytetrack *e) {
     for (auto &p : e->pipe) {
         for (void *d : {(void *)p.d_in, (void *)p.d_off, (void *)p.d_pack, (void *)p.d_pack_off,
-                        (void *)p.d_cnt, (void *)p.d_in32})
+                        (void *)p.d_in32})
             if (d) (void)hipFree(d);
         for (void *h : {(void *)p.h_in, (void *)p.h_off, (void *)p.h_pack, (void *)p.h_pack_off,
                         (void *)p.h_cnt, (void *)p.h_nid, (void *)p.h_in32})
@@ -4184,22 +4027,14 @@ int pipe_slot_ready(yta_bytetrack *e, yta_bytetrack::PipeSlot &p, long long dets
         YTA_HIP(hipHostGetDevicePointer((void **)&p.m_cnt, p.h_cnt, 0));
         YTA_HIP(hipHostMalloc((void **)&p.h_nid, sizeof(long long) * S, hipHostMallocDefault));
     }
-    if (dets > p.in_cap) {   // detections and packed rows: both bounded by the frame's dets
-        for (void *d : {(void *)p.d_in, (void *)p.d_pack})
-            if (d) (void)hipFree(d);
-        for (void *h : {(void *)p.h_in, (void *)p.h_pack})
-            if (h) (void)hipHostFree(h);
-        p.d_in = p.h_in = p.d_pack = p.h_pack = nullptr;
-        p.in_cap = p.pack_cap = 0;
-        const long long cap = std::max<long long>(dets + dets / 8, 1024);
-        YTA_HIP(hipMalloc((void **)&p.d_in, sizeof(double) * 6 * cap));
-        YTA_HIP(hipHostMalloc((void **)&p.h_in, sizeof(double) * 6 * cap, hipHostMallocDefault));
-        YTA_HIP(hipMalloc((void **)&p.d_pack, sizeof(double) * 8 * cap));
-        YTA_HIP(hipHostMalloc((void **)&p.h_pack, sizeof(double) * 8 * cap,
-                              hipHostMallocMapped | hipHostMallocCoherent));
-        YTA_HIP(hipHostGetDevicePointer((void **)&p.m_pack, p.h_pack, 0));
-        p.in_cap = p.pack_cap = cap;
-    }
+    // detections and packed rows: both bounded by the frame's dets
+    const long long cap = std::max<long long>(dets + dets / 8, 1024);
+    int rc = grow_pair(&p.d_in, &p.h_in, &p.in_cap, dets, sizeof(double) * 6, cap);
+    if (rc || dets <= p.pack_cap) return rc;
+    rc = grow_pair(&p.d_pack, &p.h_pack, &p.pack_cap, dets, sizeof(double) * 8, cap,
+                   hipHostMallocMapped | hipHostMallocCoherent);
+    if (rc) return rc;
+    YTA_HIP(hipHostGetDevicePointer((void **)&p.m_pack, p.h_pack, 0));
     return YTA_OK;
 }
 
@@ -4211,13 +4046,11 @@ int pipe_enqueue_in(yta_bytetrack *e, yta_bytetrack::PipeSlot &p, const double *
     // this slot's last frame was collected (its events completed): its buffers are free
     if (p.t_ev[0]) YTA_HIP(hipEventRecord(p.t_ev[0], p.s_in));
     memcpy(p.h_off, det_offsets, sizeof(int) * (S + 1));
-    auto ts = std::chrono::steady_clock::now();
+    auto ts = HostClock::now();
     if (!pipe_off_kernel())   // else the compute stream reads them from the mapped h_off
         YTA_HIP(hipMemcpyAsync(p.d_off, p.h_off, sizeof(int) * (S + 1), hipMemcpyHostToDevice,
                                p.s_in));
-    e->pstat[PS_SMALL_H2D_MS] += std::chrono::duration<double, std::milli>(
-                                     std::chrono::steady_clock::now() - ts)
-                                     .count();
+    e->pstat[PS_SMALL_H2D_MS] += ms_since(ts);
     p.direct_in = false;
     p.in_bytes = 0;
     if (total && dets32) {   // float32 rows: half the bytes over the link, widened on the device
@@ -4228,31 +4061,17 @@ int pipe_enqueue_in(yta_bytetrack *e, yta_bytetrack::PipeSlot &p, const double *
     } else if (total) {
         const size_t bytes = sizeof(double) * 6 * total;
         p.in_bytes = (long long)bytes;
-        ts = std::chrono::steady_clock::now();
-        const bool pinned_in = host_pinned(dets, bytes);
-        e->pstat[PS_PINNED_CHECK_MS] += std::chrono::duration<double, std::milli>(
-                                            std::chrono::steady_clock::now() - ts)
-                                            .count();
-        if (pinned_in) {   // straight from the caller (kept until collected)
-            p.direct_in = true;
-            const auto t0 = std::chrono::steady_clock::now();
+        ts = HostClock::now();
+        p.direct_in = host_pinned(dets, bytes);
+        e->pstat[PS_PINNED_CHECK_MS] += ms_since(ts);
+        const auto t0 = HostClock::now();
+        if (p.direct_in) {   // straight from the caller (kept until collected)
             YTA_HIP(copy_pieces(p.d_in, dets, bytes, hipMemcpyHostToDevice, p.s_in));
-            e->pstat[PS_H2D_CALL_MS] += std::chrono::duration<double, std::milli>(
-                                            std::chrono::steady_clock::now() - t0)
-                                            .count();
-        } else {   // staged: chunk k's DMA overlaps chunk k+1's host copy
-            const auto t0 = std::chrono::steady_clock::now();
-            const size_t ch = stage_chunk(bytes);
-            for (size_t o = 0; o < bytes; o += ch) {
-                const size_t n = std::min(ch, bytes - o);
-                par_copy(e, (char *)p.h_in + o, (const char *)dets + o, n);
-                YTA_HIP(hipMemcpyAsync((char *)p.d_in + o, (char *)p.h_in + o, n,
-                                       hipMemcpyHostToDevice, p.s_in));
-            }
-            e->pstat[PS_STAGE_IN_MS] += std::chrono::duration<double, std::milli>(
-                                            std::chrono::steady_clock::now() - t0)
-                                            .count();
+        } else {   // staged through the slot's page-locked buffer
+            rc = stage_h2d(e, p.d_in, p.h_in, dets, bytes, p.s_in);
+            if (rc) return rc;
         }
+        e->pstat[p.direct_in ? PS_H2D_CALL_MS : PS_STAGE_IN_MS] += ms_since(t0);
     }
     e->pstat[p.direct_in ? PS_IN_DIRECT : PS_IN_STAGED] += (double)p.in_bytes;
     if (p.t_ev[1]) YTA_HIP(hipEventRecord(p.t_ev[1], p.s_in));
@@ -4282,12 +4101,10 @@ int pipe_enqueue_run(yta_bytetrack *e, yta_bytetrack::PipeSlot &p, const long lo
         rc = widen_f32(p.d_in32, p.d_in, 6 * total, e->stream);
         if (rc) return rc;
     }
-    const auto tl = std::chrono::steady_clock::now();
+    const auto tl = HostClock::now();
     rc = launch_pipeline(e, p.d_in, p.d_off, e->out_own, nullptr);
     if (rc) return rc;
-    e->pstat[PS_LAUNCH_MS] += std::chrono::duration<double, std::milli>(
-                                  std::chrono::steady_clock::now() - tl)
-                                  .count();
+    e->pstat[PS_LAUNCH_MS] += ms_since(tl);
     hipLaunchKernelGGL(k_out_offsets_scan, dim3(1), dim3(OFFS_T), 0, e->stream, e->a.cnt, S,
                        e->CAP, p.d_pack_off, p.m_pack_off);
     hipLaunchKernelGGL(k_pack_out, dim3(S), dim3(256), 0, e->stream, e->out_own, (long long)e->CAP,
@@ -4303,14 +4120,12 @@ int pipe_enqueue_run(yta_bytetrack *e, yta_bytetrack::PipeSlot &p, const long lo
     if (p.t_ev[4]) YTA_HIP(hipEventRecord(p.t_ev[4], e->s_out));
     p.user_out = out;
     p.rows_bound = total;
-    auto ts = std::chrono::steady_clock::now();
+    const auto ts = HostClock::now();
     void *out_dev = nullptr;
     p.direct_out = total > 0 && host_pinned(out, sizeof(double) * 8 * total, &out_dev);
-    e->pstat[PS_PINNED_CHECK_MS] += std::chrono::duration<double, std::milli>(
-                                        std::chrono::steady_clock::now() - ts)
-                                        .count();
+    e->pstat[PS_PINNED_CHECK_MS] += ms_since(ts);
     if (total) {
-        const auto t0 = std::chrono::steady_clock::now();
+        const auto t0 = HostClock::now();
         void *dst_dev = p.direct_out ? out_dev : (void *)p.m_pack;
         if (pipe_kernel_d2h() && dst_dev) {   // the rows stored by a kernel (k_rows_to_host)
             hipLaunchKernelGGL(k_rows_to_host, dim3(pipe_d2h_blocks()), dim3(256), 0, e->s_out,
@@ -4320,9 +4135,7 @@ int pipe_enqueue_run(yta_bytetrack *e, yta_bytetrack::PipeSlot &p, const long lo
             YTA_HIP(copy_pieces(p.direct_out ? out : p.h_pack, p.d_pack,
                                 sizeof(double) * 8 * total, hipMemcpyDeviceToHost, e->s_out));
         }
-        e->pstat[PS_D2H_CALL_MS] += std::chrono::duration<double, std::milli>(
-                                        std::chrono::steady_clock::now() - t0)
-                                        .count();
+        e->pstat[PS_D2H_CALL_MS] += ms_since(t0);
     }
     if (p.t_ev[5]) YTA_HIP(hipEventRecord(p.t_ev[5], e->s_out));
     YTA_HIP(hipEventRecord(p.out_done, e->s_out));
@@ -4388,10 +4201,7 @@ int pipe_capacity(yta_bytetrack *e, const int *det_offsets) {
     for (int s = 0; s < S; ++s)
         need_c = std::max(need_c, c[s].n_tracked + c[s].n_lost +
                                       (det_offsets[s + 1] - det_offsets[s]));
-    if (need_d > e->MAXD || need_c > e->CAP)
-        return reserve(e, need_c > e->CAP ? std::max(need_c, 2 * e->CAP) : e->CAP,
-                       need_d > e->MAXD ? std::max(need_d, 2 * e->MAXD) : e->MAXD);
-    return YTA_OK;
+    return grow_for(e, need_c, need_d);
 }
 
 int pipe_submit(yta_bytetrack *e, const double *dets, const int *det_offsets,
@@ -4424,7 +4234,7 @@ int pipe_submit(yta_bytetrack *e, const double *dets, const int *det_offsets,
     }
     int rc = pipe_slot_ready(e, p, total);
     if (rc) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = HostClock::now();
     // the copy-in first (it needs only the slot), so it overlaps any wait for capacity below
     rc = pipe_enqueue_in(e, p, dets, det_offsets, total, dets32);
     if (!rc) rc = pipe_capacity(e, det_offsets);
@@ -4433,8 +4243,7 @@ int pipe_submit(yta_bytetrack *e, const double *dets, const int *det_offsets,
         p.dirty = true;
         return rc;
     }
-    e->pstat[PS_SUBMIT_MS] +=
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    e->pstat[PS_SUBMIT_MS] += ms_since(t0);
     ++e->pipe_count;
     return YTA_OK;
 }
@@ -4446,10 +4255,10 @@ int pipe_collect(yta_bytetrack *e, long long *next_id, int *out_offsets) {
     auto &p = e->pipe[e->pipe_head];
     e->pipe_head = (e->pipe_head + 1) % PIPE_DEPTH;
     --e->pipe_count;
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = HostClock::now();
     YTA_HIP(hipEventSynchronize(p.out_done));
-    const auto t1 = std::chrono::steady_clock::now();
-    e->pstat[PS_WAIT_MS] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    const auto t1 = HostClock::now();
+    e->pstat[PS_WAIT_MS] += ms_since(t0, t1);
     if (p.t_ev[0]) {   // the frame's GPU-side phases from its timing events (all complete)
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, p.t_ev[0], p.t_ev[1]) == hipSuccess)
@@ -4476,9 +4285,7 @@ int pipe_collect(yta_bytetrack *e, long long *next_id, int *out_offsets) {
     e->pstat[p.direct_out ? PS_OUT_DIRECT : PS_OUT_STAGED] += 64.0 * (double)rows;
     if (rows > 0 && !p.direct_out) {
         par_copy(e, p.user_out, p.h_pack, sizeof(double) * 8 * rows);
-        e->pstat[PS_COPY_OUT_MS] += std::chrono::duration<double, std::milli>(
-                                        std::chrono::steady_clock::now() - t1)
-                                        .count();
+        e->pstat[PS_COPY_OUT_MS] += ms_since(t1);
     }
     return YTA_OK;
 }
@@ -4578,7 +4385,7 @@ int tensor_capacity(yta_bytetrack *e, const int *counts) {
         if (rc) return rc;
         rebase();
         ++e->tstat[TS_RESERVES];
-        rc = reserve(e, e->CAP, std::max(need_d, 2 * e->MAXD));
+        rc = grow_for(e, e->CAP, need_d);
         if (rc) return rc;
     }
     const yta_bytetrack::TSlot *k0 = nullptr;
@@ -4601,7 +4408,7 @@ int tensor_capacity(yta_bytetrack *e, const int *counts) {
         need_c = std::max<long long>(need_c, e->t_base_live[s] + counts[s]);
     if (need_c > e->CAP) {
         ++e->tstat[TS_RESERVES];
-        rc = reserve(e, std::max(need_c, 2 * e->CAP), e->MAXD);
+        rc = grow_for(e, need_c, e->MAXD);
     }
     return rc;
 }
