@@ -189,12 +189,12 @@ HS_KW = dict(det_thresh=0.0, max_age=30, min_hits=1, iou_threshold=0.3, delta_t=
 def _family(kind, S, D=32):
     if kind == "ocsort":
         from yolo_tracking_amd.trackers.ocsort import OCSortEngine
-        return lambda n: OCSortEngine(n, **OC_KW)
+        return lambda n, **kw: OCSortEngine(n, **OC_KW, **kw)
     if kind == "deepocsort":
         from yolo_tracking_amd.trackers.deepocsort import DeepOCSortEngine
-        return lambda n: DeepOCSortEngine(n, feat_dim=D, **DOC_KW)
+        return lambda n, **kw: DeepOCSortEngine(n, feat_dim=D, **DOC_KW, **kw)
     from yolo_tracking_amd.trackers.hybridsort import HybridSortEngine
-    return lambda n: HybridSortEngine(n, feat_dim=D, **HS_KW)
+    return lambda n, **kw: HybridSortEngine(n, feat_dim=D, **HS_KW, **kw)
 
 
 def _family_inputs(kind, frame):

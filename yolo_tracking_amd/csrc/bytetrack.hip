@@ -32,6 +32,7 @@
 
 #include "bytetrack.hpp"
 #include "host_pool.hpp"
+#include "oc_host.hpp"   // dalloc / DALLOC, grow_pair
 
 namespace yta {
 namespace {
@@ -3067,52 +3068,15 @@ int stage_h2d(yta_bytetrack *e, void *dev, void *pinned, const void *src, size_t
     return YTA_OK;
 }
 
-// A device buffer *d and its page-locked twin *h (host_flags) of *cap elements of elem_bytes:
-// when `need` outgrows them, both are freed (contents dropped) and allocated anew with new_cap
-// elements, the caller's growth rule.
-template <typename T>
-int grow_pair(T **d, T **h, long long *cap, long long need, size_t elem_bytes, long long new_cap,
-              unsigned host_flags = hipHostMallocDefault) {
-    if (need <= *cap) return YTA_OK;
-    if (*d) (void)hipFree(*d);
-    if (*h) (void)hipHostFree(*h);
-    *d = *h = nullptr;
-    *cap = 0;
-    YTA_HIP(hipMalloc((void **)d, elem_bytes * new_cap));
-    YTA_HIP(hipHostMalloc((void **)h, elem_bytes * new_cap, host_flags));
-    *cap = new_cap;
-    return YTA_OK;
-}
-
 // Host milliseconds from t0 to t1 (now), for the pstat accumulators
 using HostClock = std::chrono::steady_clock;
 inline double ms_since(HostClock::time_point t0, HostClock::time_point t1 = HostClock::now()) {
     return std::chrono::duration<double, std::milli>(t1 - t0).count();
 }
 
-template <typename T>
-int dalloc(yta_bytetrack *e, T **p, long long n) {
-    void *q = nullptr;
-    if (n <= 0) n = 1;
-    hipError_t err = hipMalloc(&q, sizeof(T) * (size_t)n);
-    if (err != hipSuccess) {
-        set_error("hipMalloc(%lld bytes) failed: %s", (long long)(sizeof(T) * n),
-                  hipGetErrorString(err));
-        return YTA_ERR_NOMEM;
-    }
-    e->allocs.push_back(q);
-    *p = static_cast<T *>(q);
-    return YTA_OK;
-}
-
-#define DALLOC(ptr, n)                    \
-    do {                                  \
-        int _rc = dalloc(e, &(ptr), (n)); \
-        if (_rc) return _rc;              \
-    } while (0)
-
 int bt_alloc(yta_bytetrack *e) {
     const long long S = e->S, CAP = e->CAP, MAXD = e->MAXD;
+    std::vector<void *> &allocs = e->allocs;   // DALLOC
     BtArgs &a = e->a;
     a.S = e->S;
     a.CAP = e->CAP;

@@ -27,7 +27,7 @@
 #include "kf_deep.hpp"
 #include "kf_ocsort.hpp"
 #include "ocsort_common.hpp"
-#include "subset.hpp"
+#include "oc_host.hpp"
 
 namespace yta {
 namespace {
@@ -1192,54 +1192,32 @@ __global__ void k_doc_reset(DocArgs a, int s0) {
 // ================================================================================== host engine
 using namespace yta;
 
-struct yta_deepocsort {
-    int device = 0, S = 0, CAP = 0, MAXD = 0, D = 0;
-    yta_deepocsort_params prm{};
-    hipStream_t stream = nullptr;
-    std::vector<void *> allocs;
-    DocArgs a{};
-    double *h_dets = nullptr, *d_det_in = nullptr;
-    long long det_cap = 0;
-    float *h_feat = nullptr, *d_feat = nullptr;
-    long long feat_cap = 0;
-    int *h_off = nullptr, *d_off = nullptr, *h_wh = nullptr, *d_wh = nullptr;
+struct DocBuf : OcSized<DocArgs, DocCounters> {
+    int *h_wh = nullptr, *d_wh = nullptr;
     double *h_warp = nullptr, *d_warp = nullptr;
-    DocCounters *h_cnt = nullptr;
-    size_t lds = 0;
-    StreamMask mask;   // stream-subset updates (subset.hpp)
 };
 
-namespace {
-
-template <typename T>
-int doc_dalloc(yta_deepocsort *e, T **p, long long n) {
-    void *q = nullptr;
-    if (n <= 0) n = 1;
-    hipError_t err = hipMalloc(&q, sizeof(T) * (size_t)n);
-    if (err != hipSuccess) {
-        set_error("hipMalloc(%lld bytes) failed: %s", (long long)(sizeof(T) * n),
-                  hipGetErrorString(err));
-        return YTA_ERR_NOMEM;
+struct yta_deepocsort : OcEngine<DocBuf, yta_deepocsort_params> {   // the skeleton: oc_host.hpp
+    int alloc(int cap, int maxd, DocBuf &b) const;
+    std::vector<SlotCopy> slot_arrays(DocBuf &n, const DocBuf &o) const {
+        return {{n.a.rec, o.a.rec, sizeof(DocTrack)},
+                {n.a.emb, o.a.emb, sizeof(double) * std::max(D, 1)},
+                {n.a.list, o.a.list, sizeof(int)}};
     }
-    e->allocs.push_back(q);
-    *p = static_cast<T *>(q);
-    return YTA_OK;
-}
+    void launch_reset(int s0, int n) {
+        hipLaunchKernelGGL(k_doc_reset, dim3(n), dim3(256), 0, stream, b.a, s0);
+    }
+};
 
-#define DOCALLOC(ptr, n)                      \
-    do {                                      \
-        int _rc = doc_dalloc(e, &(ptr), (n)); \
-        if (_rc) return _rc;                  \
-    } while (0)
-
-int doc_alloc(yta_deepocsort *e) {
-    const long long S = e->S, CAP = e->CAP, MAXD = e->MAXD, D = e->D;
-    DocArgs &a = e->a;
-    const yta_deepocsort_params &p = e->prm;
-    a.S = e->S;
-    a.CAP = e->CAP;
-    a.MAXD = e->MAXD;
-    a.D = e->D;
+int yta_deepocsort::alloc(int cap, int maxd, DocBuf &b) const {
+    const long long S = this->S, CAP = cap, MAXD = maxd, D = this->D;
+    std::vector<void *> &allocs = b.allocs;   // DALLOC
+    DocArgs &a = b.a;
+    const yta_deepocsort_params &p = prm;
+    a.S = this->S;
+    a.CAP = cap;
+    a.MAXD = maxd;
+    a.D = this->D;
     a.det_thresh = p.det_thresh;
     a.thr = p.iou_threshold;
     a.inertia = p.inertia;
@@ -1253,59 +1231,59 @@ int doc_alloc(yta_deepocsort *e) {
     a.embedding_off = p.embedding_off || D == 0;
     a.cmc_off = p.cmc_off;
     a.aw_off = p.aw_off;
-    DOCALLOC(a.rec, S * CAP);
-    DOCALLOC(a.emb, S * CAP * std::max<long long>(D, 1));
-    DOCALLOC(a.list, S * CAP);
-    DOCALLOC(a.free_list, S * CAP);
-    DOCALLOC(a.cnt, S);
-    DOCALLOC(a.hi_row, S * MAXD);
-    DOCALLOC(a.alpha, S * MAXD);
-    DOCALLOC(a.cbox, S * CAP);
-    DOCALLOC(a.cvel, S * CAP * 2);
-    DOCALLOC(a.ckobs, S * CAP * 5);
-    DOCALLOC(a.clast, S * CAP * 5);
-    DOCALLOC(a.nan_flag, S * CAP);
-    DOCALLOC(a.cslot, S * CAP);
+    DALLOC(a.rec, S * CAP);
+    DALLOC(a.emb, S * CAP * std::max<long long>(D, 1));
+    DALLOC(a.list, S * CAP);
+    DALLOC(a.free_list, S * CAP);
+    DALLOC(a.cnt, S);
+    DALLOC(a.hi_row, S * MAXD);
+    DALLOC(a.alpha, S * MAXD);
+    DALLOC(a.cbox, S * CAP);
+    DALLOC(a.cvel, S * CAP * 2);
+    DALLOC(a.ckobs, S * CAP * 5);
+    DALLOC(a.clast, S * CAP * 5);
+    DALLOC(a.nan_flag, S * CAP);
+    DALLOC(a.cslot, S * CAP);
     const long long mat = std::max<long long>(MAXD, 4) * CAP;
-    DOCALLOC(a.mat, S * mat);
-    DOCALLOC(a.mat2, S * mat);
-    DOCALLOC(a.emat, S * mat);
-    DOCALLOC(a.pos_q, S * MAXD * POS_K);
-    DOCALLOC(a.pos_cnt, S * MAXD);
-    DOCALLOC(a.col_e, S * CAP * POS_K);
-    DOCALLOC(a.col_cnt, S * CAP);
-    DOCALLOC(a.rw, S * MAXD);
-    DOCALLOC(a.cw, S * CAP);
-    DOCALLOC(a.cw_part, S * AW_CHUNKS * CAP * 2);
-    DOCALLOC(a.rmatch, S * MAXD);
-    DOCALLOC(a.pre_u, S * MAXD);
-    DOCALLOC(a.pre_s2, S * MAXD);
-    DOCALLOC(a.pre_x, S * MAXD);
-    DOCALLOC(a.cmatched, S * CAP);
-    DOCALLOC(a.udet, S * (MAXD + CAP));
-    DOCALLOC(a.utrk, S * (MAXD + CAP));
-    DOCALLOC(a.tmp, S * (MAXD + CAP));
-    DOCALLOC(a.upd, S * CAP);
-    DOCALLOC(a.ema_slot, S * (MAXD + CAP));
-    DOCALLOC(a.ema_row, S * (MAXD + CAP));
-    DOCALLOC(a.out, S * CAP * 8);
+    DALLOC(a.mat, S * mat);
+    DALLOC(a.mat2, S * mat);
+    DALLOC(a.emat, S * mat);
+    DALLOC(a.pos_q, S * MAXD * POS_K);
+    DALLOC(a.pos_cnt, S * MAXD);
+    DALLOC(a.col_e, S * CAP * POS_K);
+    DALLOC(a.col_cnt, S * CAP);
+    DALLOC(a.rw, S * MAXD);
+    DALLOC(a.cw, S * CAP);
+    DALLOC(a.cw_part, S * AW_CHUNKS * CAP * 2);
+    DALLOC(a.rmatch, S * MAXD);
+    DALLOC(a.pre_u, S * MAXD);
+    DALLOC(a.pre_s2, S * MAXD);
+    DALLOC(a.pre_x, S * MAXD);
+    DALLOC(a.cmatched, S * CAP);
+    DALLOC(a.udet, S * (MAXD + CAP));
+    DALLOC(a.utrk, S * (MAXD + CAP));
+    DALLOC(a.tmp, S * (MAXD + CAP));
+    DALLOC(a.upd, S * CAP);
+    DALLOC(a.ema_slot, S * (MAXD + CAP));
+    DALLOC(a.ema_row, S * (MAXD + CAP));
+    DALLOC(a.out, S * CAP * 8);
     const long long n = std::max(CAP, MAXD);
     a.lap_ws_stride = oc_lap_ws_stride(n);
     a.arr_chip = MAXD >= ARR_CHIP_MIN_DETS;
     if (const char *v = getenv("YTA_ARR_CHIP")) a.arr_chip = atoi(v);
     if (const char *v = getenv("YTA_DOC_DENSE")) a.force_dense = atoi(v) != 0;
-    DOCALLOC(a.lap_ws, S * a.lap_ws_stride);
+    DALLOC(a.lap_ws, S * a.lap_ws_stride);
     a.lap_csr = nullptr;
     a.lap_csr_stride = n >= LAPB_MIN_N && lap_sparse_on() ? (lap_csr_bytes(n) + 255) & ~255LL : 0;
-    if (a.lap_csr_stride) DOCALLOC(a.lap_csr, S * a.lap_csr_stride);
-    e->lds = (size_t)oc_lds_bytes(CAP, MAXD);
-    DOCALLOC(e->d_off, S + 1);
-    DOCALLOC(e->d_wh, 2 * S);
-    DOCALLOC(e->d_warp, 6 * S);
-    YTA_HIP(hipHostMalloc((void **)&e->h_off, sizeof(int) * (S + 1), hipHostMallocDefault));
-    YTA_HIP(hipHostMalloc((void **)&e->h_wh, sizeof(int) * 2 * S, hipHostMallocDefault));
-    YTA_HIP(hipHostMalloc((void **)&e->h_warp, sizeof(double) * 6 * S, hipHostMallocDefault));
-    YTA_HIP(hipHostMalloc((void **)&e->h_cnt, sizeof(DocCounters) * S, hipHostMallocDefault));
+    if (a.lap_csr_stride) DALLOC(a.lap_csr, S * a.lap_csr_stride);
+    b.lds = (size_t)oc_lds_bytes(CAP, MAXD);
+    DALLOC(b.d_off, S + 1);
+    DALLOC(b.d_wh, 2 * S);
+    DALLOC(b.d_warp, 6 * S);
+    YTA_HIP(b.pin(&b.h_off, S + 1));
+    YTA_HIP(b.pin(&b.h_wh, 2 * S));
+    YTA_HIP(b.pin(&b.h_warp, 6 * S));
+    YTA_HIP(b.pin(&b.h_cnt, S));
     YTA_HIP(hipFuncSetAttribute((const void *)k_doc_lap, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)LAP_LDS_MAX));
     YTA_HIP(hipFuncSetAttribute((const void *)k_doc_assoc,
@@ -1317,21 +1295,11 @@ int doc_alloc(yta_deepocsort *e) {
     return YTA_OK;
 }
 
-void doc_release(yta_deepocsort *e) {
-    for (void *p : e->allocs) (void)hipFree(p);
-    e->allocs.clear();
-    if (e->h_off) (void)hipHostFree(e->h_off);
-    if (e->h_wh) (void)hipHostFree(e->h_wh);
-    if (e->h_warp) (void)hipHostFree(e->h_warp);
-    if (e->h_cnt) (void)hipHostFree(e->h_cnt);
-    e->h_off = e->h_wh = nullptr;
-    e->h_warp = nullptr;
-    e->h_cnt = nullptr;
-}
+namespace {
 
 int doc_launch(yta_deepocsort *e, const double *d_dets, const int *d_off, const float *d_feat,
                const double *d_warp, const int *d_wh, double *out, int *out_counts) {
-    DocArgs &a = e->a;
+    DocArgs &a = e->b.a;
     a.det_in = d_dets;
     a.det_off = d_off;
     a.det_feat = d_feat;
@@ -1390,12 +1358,12 @@ int doc_launch(yta_deepocsort *e, const double *d_dets, const int *d_off, const 
     hipLaunchKernelGGL(k_doc_lap, dim3(a.S), dim3(LAP_T), (size_t)lap_kernel_lds(a.CAP, a.MAXD),
                        e->stream, a);
     YTA_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_doc_assoc, dim3(a.S), dim3(OC_T), e->lds, e->stream, a);
+    hipLaunchKernelGGL(k_doc_assoc, dim3(a.S), dim3(OC_T), e->b.lds, e->stream, a);
     YTA_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_doc_ocr, dim3((unsigned)std::max(4, 2048 / a.S), a.S), dim3(256), 0,
                        e->stream, a);
     YTA_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_doc_assoc_b, dim3(a.S), dim3(OC_T), e->lds, e->stream, a);
+    hipLaunchKernelGGL(k_doc_assoc_b, dim3(a.S), dim3(OC_T), e->b.lds, e->stream, a);
     YTA_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_doc_upd, dim3((a.CAP + DOC_TRK_T - 1) / DOC_TRK_T, a.S), dim3(DOC_TRK_T), 0,
                        e->stream, a);
@@ -1410,105 +1378,22 @@ int doc_launch(yta_deepocsort *e, const double *d_dets, const int *d_off, const 
     return YTA_OK;
 }
 
-int doc_read_counters(yta_deepocsort *e) {
-    YTA_HIP(hipMemcpyAsync(e->h_cnt, e->a.cnt, sizeof(DocCounters) * e->S, hipMemcpyDeviceToHost,
+// feats holds the rows of the kept detections (conf > det_thresh), packed: scattered to their
+// detection's row of the staging pair, which goes to the device whole.
+int doc_stage_feats(yta_deepocsort *e, const double *dets, const float *feats, long long total) {
+    const int D = e->D;
+    if (D == 0 || !total) return YTA_OK;
+    const int rc = oc_grow_feats(e, total);
+    if (rc) return rc;
+    long long k = 0;
+    for (long long r = 0; r < total; ++r)
+        if (dets[r * 6 + 4] > e->prm.det_thresh) {
+            YTA_CHECK(feats, YTA_ERR_INVALID, "null feats with kept detections");
+            memcpy(e->h_feat + r * D, feats + k * D, sizeof(float) * D);
+            ++k;
+        }
+    YTA_HIP(hipMemcpyAsync(e->d_feat, e->h_feat, sizeof(float) * D * total, hipMemcpyHostToDevice,
                            e->stream));
-    YTA_HIP(host_wait(e->stream));
-    return YTA_OK;
-}
-
-int doc_check_errors(yta_deepocsort *e) {
-    for (int s = 0; s < e->S; ++s) {
-        const int err = e->h_cnt[s].err;
-        if (err) {
-            set_error("stream %d: device error flags 0x%x (%s%s%s%s)", s, err,
-                      err & ERR_GIOU ? "giou enclosure not positive (iou.py:58 assert) " : "",
-                      err & ERR_SOLVER ? "assignment solver failure " : "",
-                      err & ERR_TRACK_CAPACITY ? "track capacity exceeded " : "",
-                      err & ERR_DET_CAPACITY ? "too many detections " : "");
-            return (err & (ERR_TRACK_CAPACITY | ERR_DET_CAPACITY)) ? YTA_ERR_CAPACITY
-                   : (err & ERR_GIOU)                              ? YTA_ERR_INVALID
-                                                                   : YTA_ERR_HIP;
-        }
-    }
-    return YTA_OK;
-}
-
-int doc_reserve(yta_deepocsort *e, int cap, int maxd) {
-    if (cap <= e->CAP && maxd <= e->MAXD) return YTA_OK;
-    cap = std::max(cap, e->CAP);
-    maxd = std::max(maxd, e->MAXD);
-    YTA_HIP(host_wait(e->stream));
-    yta_deepocsort *n = new (std::nothrow) yta_deepocsort();
-    YTA_CHECK(n, YTA_ERR_NOMEM, "out of host memory");
-    n->device = e->device;
-    n->S = e->S;
-    n->CAP = cap;
-    n->MAXD = maxd;
-    n->D = e->D;
-    n->prm = e->prm;
-    n->stream = e->stream;
-    int rc = doc_alloc(n);
-    const size_t S = e->S, oc = e->CAP, nc = cap, Dd = std::max(e->D, 1);
-    auto copy2d = [&](void *dst, size_t dp, const void *src, size_t sp, size_t w) -> int {
-        YTA_HIP(hipMemcpy2DAsync(dst, dp, src, sp, w, S, hipMemcpyDeviceToDevice, e->stream));
-        return YTA_OK;
-    };
-    if (!rc) rc = copy2d(n->a.rec, nc * sizeof(DocTrack), e->a.rec, oc * sizeof(DocTrack),
-                         oc * sizeof(DocTrack));
-    if (!rc) rc = copy2d(n->a.emb, nc * Dd * 8, e->a.emb, oc * Dd * 8, oc * Dd * 8);
-    if (!rc) rc = copy2d(n->a.list, nc * 4, e->a.list, oc * 4, oc * 4);
-    if (!rc) {
-        std::vector<int> fl(nc * S), old(oc * S);
-        std::vector<DocCounters> cnt(S);
-        hipError_t he = hipMemcpyAsync(old.data(), e->a.free_list, sizeof(int) * oc * S,
-                                       hipMemcpyDeviceToHost, e->stream);
-        if (he == hipSuccess)
-            he = hipMemcpyAsync(cnt.data(), e->a.cnt, sizeof(DocCounters) * S,
-                                hipMemcpyDeviceToHost, e->stream);
-        if (he == hipSuccess) he = host_wait(e->stream);
-        if (he == hipSuccess) {
-            for (size_t s = 0; s < S; ++s) {
-                int k = 0;
-                for (int q = (int)nc - 1; q >= (int)oc; --q) fl[s * nc + k++] = q;
-                for (int q = 0; q < cnt[s].n_free; ++q) fl[s * nc + k++] = old[s * oc + q];
-                cnt[s].n_free = k;
-            }
-            he = hipMemcpy(n->a.free_list, fl.data(), sizeof(int) * nc * S, hipMemcpyHostToDevice);
-            if (he == hipSuccess)
-                he = hipMemcpy(n->a.cnt, cnt.data(), sizeof(DocCounters) * S,
-                               hipMemcpyHostToDevice);
-        }
-        if (he != hipSuccess) {
-            set_error("reserve: %s", hipGetErrorString(he));
-            rc = YTA_ERR_HIP;
-        }
-    }
-    if (rc) {
-        n->stream = nullptr;
-        doc_release(n);
-        delete n;
-        return rc;
-    }
-    memcpy(n->h_cnt, e->h_cnt, sizeof(DocCounters) * S);
-    doc_release(e);
-    e->CAP = n->CAP;
-    e->MAXD = n->MAXD;
-    e->allocs.swap(n->allocs);
-    e->a = n->a;
-    e->lds = n->lds;
-    e->h_off = n->h_off;
-    e->h_wh = n->h_wh;
-    e->h_warp = n->h_warp;
-    e->h_cnt = n->h_cnt;
-    e->d_off = n->d_off;
-    e->d_wh = n->d_wh;
-    e->d_warp = n->d_warp;
-    n->h_off = n->h_wh = nullptr;
-    n->h_warp = nullptr;
-    n->h_cnt = nullptr;
-    n->stream = nullptr;
-    delete n;
     return YTA_OK;
 }
 
@@ -1529,177 +1414,36 @@ int yta_deepocsort_create(int device, int n_streams, int track_capacity, int max
     YTA_CHECK(params->embedding_off || feat_dim > 0, YTA_ERR_INVALID,
               "embeddings need feat_dim > 0");
     YTA_CHECK(params->det_thresh < 1.0, YTA_ERR_INVALID, "det_thresh must be < 1 (trust weight)");
-    *engine = nullptr;
-    int rc = select_device(device);
-    if (rc) return rc;
-    yta_deepocsort *e = new (std::nothrow) yta_deepocsort();
-    YTA_CHECK(e, YTA_ERR_NOMEM, "out of host memory");
-    e->device = device;
-    e->S = n_streams;
-    e->CAP = track_capacity;
-    e->MAXD = max_dets;
-    e->D = params->embedding_off ? 0 : feat_dim;
-    e->prm = *params;
-    hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
-    if (he != hipSuccess) {
-        set_error("hipStreamCreate: %s", hipGetErrorString(he));
-        delete e;
-        return YTA_ERR_HIP;
-    }
-    rc = doc_alloc(e);
-    if (!rc) rc = yta_deepocsort_reset(e);
-    if (rc) {
-        yta_deepocsort_destroy(e);
-        return rc;
-    }
-    *engine = e;
-    return YTA_OK;
+    return oc_create(device, n_streams, track_capacity, max_dets,
+                     params->embedding_off ? 0 : feat_dim, params, engine);
 }
 
-int yta_deepocsort_destroy(yta_deepocsort *e) {
-    if (!e) return YTA_OK;
-    (void)hipSetDevice(e->device);
-    if (e->stream) (void)host_wait(e->stream);
-    doc_release(e);
-    e->mask.release();
-    if (e->h_dets) (void)hipHostFree(e->h_dets);
-    if (e->d_det_in) (void)hipFree(e->d_det_in);
-    if (e->h_feat) (void)hipHostFree(e->h_feat);
-    if (e->d_feat) (void)hipFree(e->d_feat);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
-    return YTA_OK;
-}
-
-int yta_deepocsort_reset(yta_deepocsort *e) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    YTA_HIP(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_doc_reset, dim3(e->S), dim3(256), 0, e->stream, e->a, 0);
-    YTA_HIP(hipGetLastError());
-    YTA_HIP(host_wait(e->stream));
-    memset(e->h_cnt, 0, sizeof(DocCounters) * e->S);
-    return YTA_OK;
-}
-
+int yta_deepocsort_destroy(yta_deepocsort *e) { return oc_destroy(e); }
+int yta_deepocsort_reset(yta_deepocsort *e) { return oc_reset(e); }
 int yta_deepocsort_capacity(yta_deepocsort *e, int *track_capacity, int *max_dets) {
-    YTA_CHECK(e && track_capacity && max_dets, YTA_ERR_INVALID, "null argument");
-    *track_capacity = e->CAP;
-    *max_dets = e->MAXD;
-    return YTA_OK;
+    return oc_capacity(e, track_capacity, max_dets);
 }
 
 int yta_deepocsort_update(yta_deepocsort *e, const double *dets, const int *det_offsets,
                           const float *feats, const double *warps, const int *img_wh,
                           long long *next_id, double *out, int out_capacity, int *out_offsets) {
     YTA_CHECK(e && det_offsets && out_offsets, YTA_ERR_INVALID, "null argument");
-    YTA_HIP(hipSetDevice(e->device));
-    const int S = e->S;
-    YTA_CHECK(det_offsets[0] == 0, YTA_ERR_INVALID, "det_offsets[0] must be 0");
-    YTA_CHECK(img_wh || e->prm.asso_func != 4, YTA_ERR_INVALID, "centroid needs img_wh");
-    int need_d = e->MAXD, need_c = e->CAP;
-    for (int s = 0; s < S; ++s) {
-        const int m = det_offsets[s + 1] - det_offsets[s];
-        YTA_CHECK(m >= 0, YTA_ERR_INVALID, "det_offsets must be non-decreasing");
-        need_d = std::max(need_d, m);
-        need_c = std::max(need_c, e->h_cnt[s].n_trk + m);
-    }
-    // every output row is a track matched to or born from one of this frame's detections, so
-    // det_offsets[S] rows always suffice; checked before anything moves (the frame is not consumed)
-    YTA_CHECK(out_capacity >= det_offsets[S], YTA_ERR_CAPACITY,
-              "out holds %d rows, the call needs det_offsets[S] = %d", out_capacity, det_offsets[S]);
-    if (need_d > e->MAXD || need_c > e->CAP) {
-        const int rc = doc_reserve(e, need_c > e->CAP ? std::max(need_c, 2 * e->CAP) : e->CAP,
-                                   need_d > e->MAXD ? std::max(need_d, 2 * e->MAXD) : e->MAXD);
-        if (rc) return rc;
-    }
-    const long long total = det_offsets[S];
+    long long total = 0;
+    int rc = oc_begin_frame(e, det_offsets, img_wh != nullptr, out_capacity, &total);
+    if (rc) return rc;
     YTA_CHECK(total == 0 || dets, YTA_ERR_INVALID, "null dets");
-    if (total > e->det_cap) {
-        if (e->d_det_in) (void)hipFree(e->d_det_in);
-        if (e->h_dets) (void)hipHostFree(e->h_dets);
-        e->d_det_in = nullptr;
-        e->h_dets = nullptr;
-        e->det_cap = 0;
-        const long long cap = std::max<long long>(2 * total, 1024);
-        YTA_HIP(hipMalloc((void **)&e->d_det_in, sizeof(double) * 6 * cap));
-        YTA_HIP(hipHostMalloc((void **)&e->h_dets, sizeof(double) * 6 * cap, hipHostMallocDefault));
-        e->det_cap = cap;
-    }
-    if (total) {
-        memcpy(e->h_dets, dets, sizeof(double) * 6 * total);
-        YTA_HIP(hipMemcpyAsync(e->d_det_in, e->h_dets, sizeof(double) * 6 * total,
-                               hipMemcpyHostToDevice, e->stream));
-    }
-    const int D = e->D;
-    if (D > 0 && total) {   // feats: rows of the kept detections (conf > det_thresh), packed
-        if (total > e->feat_cap) {
-            if (e->d_feat) (void)hipFree(e->d_feat);
-            if (e->h_feat) (void)hipHostFree(e->h_feat);
-            e->d_feat = nullptr;
-            e->h_feat = nullptr;
-            e->feat_cap = 0;
-            const long long cap = std::max<long long>(2 * total, 1024);
-            YTA_HIP(hipMalloc((void **)&e->d_feat, sizeof(float) * D * cap));
-            YTA_HIP(hipHostMalloc((void **)&e->h_feat, sizeof(float) * D * cap,
-                                  hipHostMallocDefault));
-            e->feat_cap = cap;
-        }
-        long long k = 0;
-        for (long long r = 0; r < total; ++r)
-            if (dets[r * 6 + 4] > e->prm.det_thresh) {
-                YTA_CHECK(feats, YTA_ERR_INVALID, "null feats with kept detections");
-                memcpy(e->h_feat + r * D, feats + k * D, sizeof(float) * D);
-                ++k;
-            }
-        YTA_HIP(hipMemcpyAsync(e->d_feat, e->h_feat, sizeof(float) * D * total,
-                               hipMemcpyHostToDevice, e->stream));
-    }
-    memcpy(e->h_off, det_offsets, sizeof(int) * (S + 1));
-    YTA_HIP(hipMemcpyAsync(e->d_off, e->h_off, sizeof(int) * (S + 1), hipMemcpyHostToDevice,
-                           e->stream));
-    if (img_wh) {
-        memcpy(e->h_wh, img_wh, sizeof(int) * 2 * S);
-        YTA_HIP(hipMemcpyAsync(e->d_wh, e->h_wh, sizeof(int) * 2 * S, hipMemcpyHostToDevice,
-                               e->stream));
-    }
-    if (warps) {
-        memcpy(e->h_warp, warps, sizeof(double) * 6 * S);
-        YTA_HIP(hipMemcpyAsync(e->d_warp, e->h_warp, sizeof(double) * 6 * S,
-                               hipMemcpyHostToDevice, e->stream));
-    }
-    if (next_id) {
-        for (int s = 0; s < S; ++s) e->h_cnt[s].next_id = next_id[s];
-        YTA_HIP(hipMemcpy2DAsync(&e->a.cnt[0].next_id, sizeof(DocCounters),
-                                 &e->h_cnt[0].next_id, sizeof(DocCounters), sizeof(long long), S,
-                                 hipMemcpyHostToDevice, e->stream));
-    }
-    int rc = doc_launch(e, e->d_det_in, e->d_off, e->d_feat, warps ? e->d_warp : nullptr,
-                        img_wh ? e->d_wh : nullptr, e->a.out, nullptr);
+    const int S = e->S;
+    DocBuf &b = e->b;
+    rc = oc_stage_dets(e, dets, total);
+    if (!rc) rc = doc_stage_feats(e, dets, feats, total);
+    if (!rc) rc = oc_stage_offsets(e, det_offsets);
+    if (!rc && img_wh) rc = oc_stage(e, b.d_wh, b.h_wh, img_wh, sizeof(int) * 2 * S);
+    if (!rc && warps) rc = oc_stage(e, b.d_warp, b.h_warp, warps, sizeof(double) * 6 * S);
+    if (!rc) rc = oc_put_next_id(e, next_id);
+    if (!rc) rc = doc_launch(e, e->d_det_in, b.d_off, e->d_feat, warps ? b.d_warp : nullptr,
+                             img_wh ? b.d_wh : nullptr, b.a.out, nullptr);
     if (rc) return rc;
-    rc = doc_read_counters(e);
-    if (rc) return rc;
-    if (next_id)   // the device counters have advanced: hand them back even on an error below
-        for (int s = 0; s < S; ++s) next_id[s] = e->h_cnt[s].next_id;
-    rc = doc_check_errors(e);
-    if (rc) return rc;
-    long long rows = 0;
-    out_offsets[0] = 0;
-    for (int s = 0; s < S; ++s) {
-        rows += e->h_cnt[s].n_out;
-        out_offsets[s + 1] = (int)rows;
-    }
-    YTA_CHECK(rows <= out_capacity, YTA_ERR_CAPACITY, "output needs %lld rows > capacity %d", rows,
-              out_capacity);
-    YTA_CHECK(rows == 0 || out, YTA_ERR_INVALID, "null out");
-    for (int s = 0; s < S; ++s) {
-        const int n = e->h_cnt[s].n_out;
-        if (n)
-            YTA_HIP(hipMemcpyAsync(out + (long long)out_offsets[s] * 8,
-                                   e->a.out + (long long)s * e->CAP * 8, sizeof(double) * 8 * n,
-                                   hipMemcpyDeviceToHost, e->stream));
-    }
-    YTA_HIP(host_wait(e->stream));
-    return YTA_OK;
+    return oc_end_frame(e, next_id, out, out_capacity, out_offsets);
 }
 
 int yta_deepocsort_update_device(yta_deepocsort *e, const double *d_dets,
@@ -1712,27 +1456,23 @@ int yta_deepocsort_update_device(yta_deepocsort *e, const double *d_dets,
     return doc_launch(e, d_dets, d_det_offsets, d_feats, d_warps, d_img_wh, d_out, d_out_counts);
 }
 
-int yta_deepocsort_sync(yta_deepocsort *e) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    const int rc = doc_read_counters(e);
-    if (rc) return rc;
-    return doc_check_errors(e);
-}
+int yta_deepocsort_sync(yta_deepocsort *e) { return oc_sync(e); }
 
 int yta_deepocsort_get_state(yta_deepocsort *e, int stream, int *n_tracks, long long *ints,
                              double *x, double *P, double *emb) {
     YTA_CHECK(e && n_tracks && ints && x && P, YTA_ERR_INVALID, "null argument");
     YTA_CHECK(stream >= 0 && stream < e->S, YTA_ERR_INVALID, "bad stream %d", stream);
     YTA_HIP(hipSetDevice(e->device));
-    const int rc = doc_read_counters(e);
+    const int rc = oc_read_counters(e);
     if (rc) return rc;
-    const DocCounters c = e->h_cnt[stream];
-    const long long tb = (long long)stream * e->CAP;
+    const DocCounters c = e->b.h_cnt[stream];
+    const DocArgs &a = e->b.a;
+    const long long tb = (long long)stream * a.CAP;
     std::vector<int> lst(c.n_trk);
-    std::vector<DocTrack> rec(e->CAP);
+    std::vector<DocTrack> rec(a.CAP);
     if (c.n_trk)
-        YTA_HIP(hipMemcpy(lst.data(), e->a.list + tb, sizeof(int) * c.n_trk, hipMemcpyDeviceToHost));
-    YTA_HIP(hipMemcpy(rec.data(), e->a.rec + tb, sizeof(DocTrack) * e->CAP, hipMemcpyDeviceToHost));
+        YTA_HIP(hipMemcpy(lst.data(), a.list + tb, sizeof(int) * c.n_trk, hipMemcpyDeviceToHost));
+    YTA_HIP(hipMemcpy(rec.data(), a.rec + tb, sizeof(DocTrack) * a.CAP, hipMemcpyDeviceToHost));
     for (int i = 0; i < c.n_trk; ++i) {
         const DocTrack &r = rec[lst[i]];
         long long *ii = ints + 7LL * i;
@@ -1751,7 +1491,7 @@ int yta_deepocsort_get_state(yta_deepocsort *e, int stream, int *n_tracks, long 
                 for (int b0 = 0; b0 < 4; ++b0)
                     M[dk_glob(g, a0) * 8 + dk_glob(g, b0)] = r.kf.p[g][4 * a0 + b0];
         if (emb && e->D)
-            YTA_HIP(hipMemcpy(emb + (long long)i * e->D, e->a.emb + (tb + lst[i]) * e->D,
+            YTA_HIP(hipMemcpy(emb + (long long)i * e->D, a.emb + (tb + lst[i]) * e->D,
                               sizeof(double) * e->D, hipMemcpyDeviceToHost));
     }
     *n_tracks = c.n_trk;
@@ -1760,11 +1500,11 @@ int yta_deepocsort_get_state(yta_deepocsort *e, int stream, int *n_tracks, long 
 
 int yta_deepocsort_stats(yta_deepocsort *e, long long *stats) {
     YTA_CHECK(e && stats, YTA_ERR_INVALID, "null argument");
-    const int rc = doc_read_counters(e);
+    const int rc = oc_read_counters(e);
     if (rc) return rc;
     for (int k = 0; k < 8; ++k) stats[k] = 0;
     for (int s = 0; s < e->S; ++s) {
-        const DocCounters &c = e->h_cnt[s];
+        const DocCounters &c = e->b.h_cnt[s];
         const long long v[8] = {c.n_dets, c.n_high, 0, c.n_trk, c.n_out, c.n_births, c.lap_calls,
                                 c.fast_path};
         for (int k = 0; k < 8; ++k) stats[k] += v[k];
@@ -1811,25 +1551,10 @@ int yta_kf8_run(int device, int n, int steps, const double *b0, const double *b,
 }
 
 int yta_deepocsort_lap_stats(yta_deepocsort *e, long long *stats, int n) {
-    YTA_CHECK(e && (stats || n <= 0), YTA_ERR_INVALID, "null argument");
-    const int rc = doc_read_counters(e);
-    if (rc) return rc;
-    long long v[YTA_LAP_STATS] = {};
-    for (int s = 0; s < e->S; ++s) {
-        const LapStats &l = e->h_cnt[s].ls;
-        v[0] += l.transposed;
-        v[1] += l.uncertified;
-        v[2] += l.replays;
-        v[3] += l.reduced;
-    }
-    for (int k = 0; k < n && k < YTA_LAP_STATS; ++k) stats[k] = v[k];
-    return YTA_OK;
+    return oc_lap_stats(e, stats, n);
 }
-
 int yta_deepocsort_hip_stream(yta_deepocsort *e, void **stream) {
-    YTA_CHECK(e && stream, YTA_ERR_INVALID, "null argument");
-    *stream = (void *)e->stream;
-    return YTA_OK;
+    return oc_hip_stream(e, stream);
 }
 
 #ifdef YTA_STAMPS
@@ -1842,56 +1567,39 @@ int yta_deepocsort_debug_stamps(unsigned long long *out) {
 
 // ---- stream subsets (subset.hpp): the listed streams updated, every other stream untouched
 int yta_deepocsort_reset_stream(yta_deepocsort *e, int stream) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    YTA_CHECK(stream >= 0 && stream < e->S, YTA_ERR_INVALID, "stream %d outside 0..%d", stream,
-              e->S - 1);
-    YTA_HIP(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_doc_reset, dim3(1), dim3(256), 0, e->stream, e->a, stream);
-    YTA_HIP(hipGetLastError());
-    YTA_HIP(host_wait(e->stream));
-    return doc_read_counters(e);
+    return oc_reset_stream(e, stream);
 }
 
-int yta_deepocsort_update_device_masked(yta_deepocsort *e, const int *d_active, const double *d_dets, const int *d_det_offsets, const float *d_feats, const double *d_warps, const int *d_img_wh, double *d_out, int *d_out_counts) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    e->mask.req_dev = d_active;
-    const int rc = yta_deepocsort_update_device(e, d_dets, d_det_offsets, d_feats, d_warps, d_img_wh, d_out, d_out_counts);
-    e->mask.req_dev = nullptr;
-    return rc;
+int yta_deepocsort_update_device_masked(yta_deepocsort *e, const int *d_active,
+                                        const double *d_dets, const int *d_det_offsets,
+                                        const float *d_feats, const double *d_warps,
+                                        const int *d_img_wh, double *d_out, int *d_out_counts) {
+    return oc_update_device_masked(e, d_active, [&] {
+        return yta_deepocsort_update_device(e, d_dets, d_det_offsets, d_feats, d_warps, d_img_wh,
+                                            d_out, d_out_counts);
+    });
 }
 
-int yta_deepocsort_update_streams(yta_deepocsort *e, int n_streams, const int *stream_ids, const double *dets, const int *det_offsets, const float *feats, const double *warps, const int *img_wh,
-                           long long *next_id, double *out, int out_capacity, int *out_offsets) {
-    YTA_CHECK(e && out_offsets, YTA_ERR_INVALID, "null argument");
-    YTA_HIP(hipSetDevice(e->device));
-    const int S = e->S;
-    std::vector<int> mask, off, full_oo(S + 1, 0);
-    int rc = subset_expand(S, n_streams, stream_ids, det_offsets, mask, off);
-    if (rc) return rc;
-    std::vector<long long> nid(S);
-    if (next_id) {   // the skipped streams keep their device counters: read them first
-        rc = doc_read_counters(e);
-        if (rc) return rc;
-        for (int s = 0; s < S; ++s) nid[s] = e->h_cnt[s].next_id;
-        for (int k = 0; k < n_streams; ++k) nid[stream_ids[k]] = next_id[k];
-    }
-    std::vector<int> wh;
-    if (img_wh) wh = subset_spread<int>(S, n_streams, stream_ids, img_wh, 2, 1);
-    std::vector<double> w;
-    if (warps) {
-        w = subset_spread<double>(S, n_streams, stream_ids, warps, 6, 0.0);
-        for (int s = 0; s < S; ++s)
-            if (!mask[s]) w[6 * s] = w[6 * s + 4] = 1.0;   // identity for the skipped streams
-    }
-    e->mask.req_host = mask.data();
-    rc = yta_deepocsort_update(e, dets, off.data(), feats, warps ? w.data() : nullptr, img_wh ? wh.data() : nullptr, next_id ? nid.data() : nullptr, out,
-                        out_capacity, full_oo.data());
-    e->mask.req_host = nullptr;
-    if (next_id)
-        for (int k = 0; k < n_streams; ++k) next_id[k] = nid[stream_ids[k]];
-    if (rc) return rc;
-    subset_compact(n_streams, stream_ids, full_oo, out_offsets);
-    return YTA_OK;
+int yta_deepocsort_update_streams(yta_deepocsort *e, int n_streams, const int *stream_ids,
+                                  const double *dets, const int *det_offsets, const float *feats,
+                                  const double *warps, const int *img_wh, long long *next_id,
+                                  double *out, int out_capacity, int *out_offsets) {
+    return oc_update_streams(
+        e, n_streams, stream_ids, det_offsets, next_id, out_offsets,
+        [&](const std::vector<int> &mask, const int *off, long long *nid, int *full_oo) {
+            const int S = e->S;
+            std::vector<int> wh;
+            if (img_wh) wh = subset_spread<int>(S, n_streams, stream_ids, img_wh, 2, 1);
+            std::vector<double> w;
+            if (warps) {
+                w = subset_spread<double>(S, n_streams, stream_ids, warps, 6, 0.0);
+                for (int s = 0; s < S; ++s)
+                    if (!mask[s]) w[6 * s] = w[6 * s + 4] = 1.0;   // identity for the skipped streams
+            }
+            return yta_deepocsort_update(e, dets, off, feats, warps ? w.data() : nullptr,
+                                         img_wh ? wh.data() : nullptr, nid, out, out_capacity,
+                                         full_oo);
+        });
 }
 
 }  // extern "C"

@@ -33,7 +33,7 @@
 #include "kf_hybrid.hpp"
 #include "kf_ocsort.hpp"   // np_sum5
 #include "ocsort_common.hpp"
-#include "subset.hpp"
+#include "oc_host.hpp"
 
 namespace yta {
 namespace {
@@ -1110,53 +1110,29 @@ __global__ void k_hs_reset(HsArgs a, int s0) {
 // ================================================================================== host engine
 using namespace yta;
 
-struct yta_hybridsort {
-    int device = 0, S = 0, CAP = 0, MAXD = 0, D = 0;
-    yta_hybridsort_params prm{};
-    hipStream_t stream = nullptr;
-    std::vector<void *> allocs;
-    HsArgs a{};
-    double *h_dets = nullptr, *d_det_in = nullptr;
-    long long det_cap = 0;
-    float *h_feat = nullptr, *d_feat = nullptr;
-    long long feat_cap = 0;
-    int *h_off = nullptr, *d_off = nullptr;
-    HsCounters *h_cnt = nullptr;
-    size_t lds = 0;
-    StreamMask mask;   // stream-subset updates (subset.hpp)
+using HsBuf = OcSized<HsArgs, HsCounters>;
+
+struct yta_hybridsort : OcEngine<HsBuf, yta_hybridsort_params> {   // the skeleton: oc_host.hpp
+    int alloc(int cap, int maxd, HsBuf &b) const;
+    std::vector<SlotCopy> slot_arrays(HsBuf &n, const HsBuf &o) const {
+        return {{n.a.rec, o.a.rec, sizeof(HsTrack)},
+                {n.a.feat, o.a.feat, sizeof(float) * D},
+                {n.a.list, o.a.list, sizeof(int)}};
+    }
+    void launch_reset(int s0, int n) {
+        hipLaunchKernelGGL(k_hs_reset, dim3(n), dim3(256), 0, stream, b.a, s0);
+    }
 };
 
-namespace {
-
-template <typename T>
-int hs_dalloc(yta_hybridsort *e, T **p, long long n) {
-    void *q = nullptr;
-    if (n <= 0) n = 1;
-    hipError_t err = hipMalloc(&q, sizeof(T) * (size_t)n);
-    if (err != hipSuccess) {
-        set_error("hipMalloc(%lld bytes) failed: %s", (long long)(sizeof(T) * n),
-                  hipGetErrorString(err));
-        return YTA_ERR_NOMEM;
-    }
-    e->allocs.push_back(q);
-    *p = static_cast<T *>(q);
-    return YTA_OK;
-}
-
-#define HSALLOC(ptr, n)                      \
-    do {                                     \
-        int _rc = hs_dalloc(e, &(ptr), (n)); \
-        if (_rc) return _rc;                 \
-    } while (0)
-
-int hs_alloc(yta_hybridsort *e) {
-    const long long S = e->S, CAP = e->CAP, MAXD = e->MAXD, D = e->D;
-    HsArgs &a = e->a;
-    const yta_hybridsort_params &p = e->prm;
-    a.S = e->S;
-    a.CAP = e->CAP;
-    a.MAXD = e->MAXD;
-    a.D = e->D;
+int yta_hybridsort::alloc(int cap, int maxd, HsBuf &b) const {
+    const long long S = this->S, CAP = cap, MAXD = maxd, D = this->D;
+    std::vector<void *> &allocs = b.allocs;   // DALLOC
+    HsArgs &a = b.a;
+    const yta_hybridsort_params &p = prm;
+    a.S = this->S;
+    a.CAP = cap;
+    a.MAXD = maxd;
+    a.D = this->D;
     a.det_thresh = p.det_thresh;
     a.thr = p.iou_threshold;
     a.inertia = p.inertia;
@@ -1164,45 +1140,45 @@ int hs_alloc(yta_hybridsort *e) {
     a.min_hits = p.min_hits;
     a.delta_t = p.delta_t;
     a.asso = p.asso_func;
-    HSALLOC(a.rec, S * CAP);
-    HSALLOC(a.feat, S * CAP * D);
-    HSALLOC(a.list, S * CAP);
-    HSALLOC(a.free_list, S * CAP);
-    HSALLOC(a.cnt, S);
-    HSALLOC(a.hi_row, S * MAXD);
-    HSALLOC(a.corr, S * MAXD);
-    HSALLOC(a.col, S * CAP);
-    HSALLOC(a.clast, S * CAP * 5);
-    HSALLOC(a.nan_flag, S * CAP);
-    HSALLOC(a.cslot, S * CAP);
+    DALLOC(a.rec, S * CAP);
+    DALLOC(a.feat, S * CAP * D);
+    DALLOC(a.list, S * CAP);
+    DALLOC(a.free_list, S * CAP);
+    DALLOC(a.cnt, S);
+    DALLOC(a.hi_row, S * MAXD);
+    DALLOC(a.corr, S * MAXD);
+    DALLOC(a.col, S * CAP);
+    DALLOC(a.clast, S * CAP * 5);
+    DALLOC(a.nan_flag, S * CAP);
+    DALLOC(a.cslot, S * CAP);
     // the cost matrix doubles as the column-record scratch of k_hs_pre (CAP records of 160 B)
     const long long mat = std::max<long long>(MAXD, (long long)sizeof(HsCol) / 8) * CAP;
-    HSALLOC(a.cost, S * mat);
-    HSALLOC(a.emat, S * mat);
-    HSALLOC(a.rmatch, S * MAXD);
-    HSALLOC(a.pre_u, S * MAXD);
-    HSALLOC(a.pre_s2, S * MAXD);
-    HSALLOC(a.pre_x, S * MAXD);
-    HSALLOC(a.cmatched, S * CAP);
-    HSALLOC(a.udet, S * (MAXD + CAP));
-    HSALLOC(a.utrk, S * (MAXD + CAP));
-    HSALLOC(a.tmp, S * (MAXD + CAP));
-    HSALLOC(a.upd, S * CAP);
-    HSALLOC(a.ema_slot, S * (MAXD + CAP));
-    HSALLOC(a.ema_row, S * (MAXD + CAP));
-    HSALLOC(a.out, S * CAP * 8);
+    DALLOC(a.cost, S * mat);
+    DALLOC(a.emat, S * mat);
+    DALLOC(a.rmatch, S * MAXD);
+    DALLOC(a.pre_u, S * MAXD);
+    DALLOC(a.pre_s2, S * MAXD);
+    DALLOC(a.pre_x, S * MAXD);
+    DALLOC(a.cmatched, S * CAP);
+    DALLOC(a.udet, S * (MAXD + CAP));
+    DALLOC(a.utrk, S * (MAXD + CAP));
+    DALLOC(a.tmp, S * (MAXD + CAP));
+    DALLOC(a.upd, S * CAP);
+    DALLOC(a.ema_slot, S * (MAXD + CAP));
+    DALLOC(a.ema_row, S * (MAXD + CAP));
+    DALLOC(a.out, S * CAP * 8);
     const long long n = std::max(CAP, MAXD);
     a.lap_ws_stride = oc_lap_ws_stride(n);
     a.arr_chip = MAXD >= ARR_CHIP_MIN_DETS;
     if (const char *v = getenv("YTA_ARR_CHIP")) a.arr_chip = atoi(v);
-    HSALLOC(a.lap_ws, S * a.lap_ws_stride);
+    DALLOC(a.lap_ws, S * a.lap_ws_stride);
     a.lap_csr = nullptr;
     a.lap_csr_stride = n >= LAPB_MIN_N && lap_sparse_on() ? (lap_csr_bytes(n) + 255) & ~255LL : 0;
-    if (a.lap_csr_stride) HSALLOC(a.lap_csr, S * a.lap_csr_stride);
-    e->lds = (size_t)oc_lds_bytes(CAP, MAXD);
-    HSALLOC(e->d_off, S + 1);
-    YTA_HIP(hipHostMalloc((void **)&e->h_off, sizeof(int) * (S + 1), hipHostMallocDefault));
-    YTA_HIP(hipHostMalloc((void **)&e->h_cnt, sizeof(HsCounters) * S, hipHostMallocDefault));
+    if (a.lap_csr_stride) DALLOC(a.lap_csr, S * a.lap_csr_stride);
+    b.lds = (size_t)oc_lds_bytes(CAP, MAXD);
+    DALLOC(b.d_off, S + 1);
+    YTA_HIP(b.pin(&b.h_off, S + 1));
+    YTA_HIP(b.pin(&b.h_cnt, S));
     YTA_HIP(hipFuncSetAttribute((const void *)k_hs_lap, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)LAP_LDS_MAX));
     YTA_HIP(hipFuncSetAttribute((const void *)k_hs_assoc,
@@ -1214,18 +1190,13 @@ int hs_alloc(yta_hybridsort *e) {
     return YTA_OK;
 }
 
-void hs_release(yta_hybridsort *e) {
-    for (void *p : e->allocs) (void)hipFree(p);
-    e->allocs.clear();
-    if (e->h_off) (void)hipHostFree(e->h_off);
-    if (e->h_cnt) (void)hipHostFree(e->h_cnt);
-    e->h_off = nullptr;
-    e->h_cnt = nullptr;
-}
+namespace {
+
+constexpr const char *HS_INF_ROW_TEXT = "infinite predicted box without NaN ";
 
 int hs_launch(yta_hybridsort *e, const double *d_dets, const int *d_off, const float *d_feat,
               double *out, int *out_counts) {
-    HsArgs &a = e->a;
+    HsArgs &a = e->b.a;
     a.det_in = d_dets;
     a.det_off = d_off;
     a.det_feat = d_feat;
@@ -1270,7 +1241,7 @@ int hs_launch(yta_hybridsort *e, const double *d_dets, const int *d_off, const f
     hipLaunchKernelGGL(k_hs_upd, dim3((a.MAXD + HS_UPD_T - 1) / HS_UPD_T, a.S), dim3(HS_UPD_T), 0,
                        e->stream, a);
     YTA_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_hs_assoc, dim3(a.S), dim3(OC_T), e->lds, e->stream, a);
+    hipLaunchKernelGGL(k_hs_assoc, dim3(a.S), dim3(OC_T), e->b.lds, e->stream, a);
     YTA_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_hs_ocr, dim3((unsigned)std::max(4, 2048 / a.S), a.S), dim3(256), 0, e->stream,
                        a);
@@ -1282,109 +1253,11 @@ int hs_launch(yta_hybridsort *e, const double *d_dets, const int *d_off, const f
                            dim3(OC_T), 0, e->stream, a);
         YTA_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_hs_assoc_b, dim3(a.S), dim3(OC_T), e->lds, e->stream, a);
+    hipLaunchKernelGGL(k_hs_assoc_b, dim3(a.S), dim3(OC_T), e->b.lds, e->stream, a);
     YTA_HIP(hipGetLastError());
     const dim3 gj((a.CAP + a.MAXD + 3) / 4, a.S);
     hipLaunchKernelGGL(k_hs_ema, gj, dim3(256), 0, e->stream, a);
     YTA_HIP(hipGetLastError());
-    return YTA_OK;
-}
-
-int hs_read_counters(yta_hybridsort *e) {
-    YTA_HIP(hipMemcpyAsync(e->h_cnt, e->a.cnt, sizeof(HsCounters) * e->S, hipMemcpyDeviceToHost,
-                           e->stream));
-    YTA_HIP(host_wait(e->stream));
-    return YTA_OK;
-}
-
-int hs_check_errors(yta_hybridsort *e) {
-    for (int s = 0; s < e->S; ++s) {
-        const int err = e->h_cnt[s].err;
-        if (err) {
-            set_error("stream %d: device error flags 0x%x (%s%s%s%s%s)", s, err,
-                      err & ERR_GIOU ? "giou enclosure not positive (iou.py:58 assert) " : "",
-                      err & ERR_SOLVER ? "assignment solver failure " : "",
-                      err & ERR_TRACK_CAPACITY ? "track capacity exceeded " : "",
-                      err & ERR_DET_CAPACITY ? "too many detections " : "",
-                      err & ERR_INF_ROW ? "infinite predicted box without NaN " : "");
-            return (err & (ERR_TRACK_CAPACITY | ERR_DET_CAPACITY)) ? YTA_ERR_CAPACITY
-                   : (err & (ERR_GIOU | ERR_INF_ROW))               ? YTA_ERR_INVALID
-                                                                   : YTA_ERR_HIP;
-        }
-    }
-    return YTA_OK;
-}
-
-int hs_reserve(yta_hybridsort *e, int cap, int maxd) {
-    if (cap <= e->CAP && maxd <= e->MAXD) return YTA_OK;
-    cap = std::max(cap, e->CAP);
-    maxd = std::max(maxd, e->MAXD);
-    YTA_HIP(host_wait(e->stream));
-    yta_hybridsort *n = new (std::nothrow) yta_hybridsort();
-    YTA_CHECK(n, YTA_ERR_NOMEM, "out of host memory");
-    n->device = e->device;
-    n->S = e->S;
-    n->CAP = cap;
-    n->MAXD = maxd;
-    n->D = e->D;
-    n->prm = e->prm;
-    n->stream = e->stream;
-    int rc = hs_alloc(n);
-    const size_t S = e->S, oc = e->CAP, nc = cap, Dd = e->D;
-    auto copy2d = [&](void *dst, size_t dp, const void *src, size_t sp, size_t w) -> int {
-        YTA_HIP(hipMemcpy2DAsync(dst, dp, src, sp, w, S, hipMemcpyDeviceToDevice, e->stream));
-        return YTA_OK;
-    };
-    if (!rc) rc = copy2d(n->a.rec, nc * sizeof(HsTrack), e->a.rec, oc * sizeof(HsTrack),
-                         oc * sizeof(HsTrack));
-    if (!rc) rc = copy2d(n->a.feat, nc * Dd * 4, e->a.feat, oc * Dd * 4, oc * Dd * 4);
-    if (!rc) rc = copy2d(n->a.list, nc * 4, e->a.list, oc * 4, oc * 4);
-    if (!rc) {
-        std::vector<int> fl(nc * S), old(oc * S);
-        std::vector<HsCounters> cnt(S);
-        hipError_t he = hipMemcpyAsync(old.data(), e->a.free_list, sizeof(int) * oc * S,
-                                       hipMemcpyDeviceToHost, e->stream);
-        if (he == hipSuccess)
-            he = hipMemcpyAsync(cnt.data(), e->a.cnt, sizeof(HsCounters) * S,
-                                hipMemcpyDeviceToHost, e->stream);
-        if (he == hipSuccess) he = host_wait(e->stream);
-        if (he == hipSuccess) {
-            for (size_t s = 0; s < S; ++s) {
-                int k = 0;
-                for (int q = (int)nc - 1; q >= (int)oc; --q) fl[s * nc + k++] = q;
-                for (int q = 0; q < cnt[s].n_free; ++q) fl[s * nc + k++] = old[s * oc + q];
-                cnt[s].n_free = k;
-            }
-            he = hipMemcpy(n->a.free_list, fl.data(), sizeof(int) * nc * S, hipMemcpyHostToDevice);
-            if (he == hipSuccess)
-                he = hipMemcpy(n->a.cnt, cnt.data(), sizeof(HsCounters) * S,
-                               hipMemcpyHostToDevice);
-        }
-        if (he != hipSuccess) {
-            set_error("reserve: %s", hipGetErrorString(he));
-            rc = YTA_ERR_HIP;
-        }
-    }
-    if (rc) {
-        n->stream = nullptr;
-        hs_release(n);
-        delete n;
-        return rc;
-    }
-    memcpy(n->h_cnt, e->h_cnt, sizeof(HsCounters) * S);
-    hs_release(e);
-    e->CAP = n->CAP;
-    e->MAXD = n->MAXD;
-    e->allocs.swap(n->allocs);
-    e->a = n->a;
-    e->lds = n->lds;
-    e->h_off = n->h_off;
-    e->h_cnt = n->h_cnt;
-    e->d_off = n->d_off;
-    n->h_off = nullptr;
-    n->h_cnt = nullptr;
-    n->stream = nullptr;
-    delete n;
     return YTA_OK;
 }
 
@@ -1404,151 +1277,32 @@ int yta_hybridsort_create(int device, int n_streams, int track_capacity, int max
               "asso_func must be 0..3 (iou, giou, diou, ciou): HybridSORT calls it without the "
               "image size centroid needs (hybridsort.py:516)");
     YTA_CHECK(feat_dim > 0, YTA_ERR_INVALID, "HybridSORT needs embeddings (feat_dim > 0)");
-    *engine = nullptr;
-    int rc = select_device(device);
-    if (rc) return rc;
-    yta_hybridsort *e = new (std::nothrow) yta_hybridsort();
-    YTA_CHECK(e, YTA_ERR_NOMEM, "out of host memory");
-    e->device = device;
-    e->S = n_streams;
-    e->CAP = track_capacity;
-    e->MAXD = max_dets;
-    e->D = feat_dim;
-    e->prm = *params;
-    hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
-    if (he != hipSuccess) {
-        set_error("hipStreamCreate: %s", hipGetErrorString(he));
-        delete e;
-        return YTA_ERR_HIP;
-    }
-    rc = hs_alloc(e);
-    if (!rc) rc = yta_hybridsort_reset(e);
-    if (rc) {
-        yta_hybridsort_destroy(e);
-        return rc;
-    }
-    *engine = e;
-    return YTA_OK;
+    return oc_create(device, n_streams, track_capacity, max_dets, feat_dim, params, engine);
 }
 
-int yta_hybridsort_destroy(yta_hybridsort *e) {
-    if (!e) return YTA_OK;
-    (void)hipSetDevice(e->device);
-    if (e->stream) (void)host_wait(e->stream);
-    hs_release(e);
-    e->mask.release();
-    if (e->h_dets) (void)hipHostFree(e->h_dets);
-    if (e->d_det_in) (void)hipFree(e->d_det_in);
-    if (e->h_feat) (void)hipHostFree(e->h_feat);
-    if (e->d_feat) (void)hipFree(e->d_feat);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
-    return YTA_OK;
-}
-
-int yta_hybridsort_reset(yta_hybridsort *e) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    YTA_HIP(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_hs_reset, dim3(e->S), dim3(256), 0, e->stream, e->a, 0);
-    YTA_HIP(hipGetLastError());
-    YTA_HIP(host_wait(e->stream));
-    memset(e->h_cnt, 0, sizeof(HsCounters) * e->S);
-    return YTA_OK;
-}
-
+int yta_hybridsort_destroy(yta_hybridsort *e) { return oc_destroy(e); }
+int yta_hybridsort_reset(yta_hybridsort *e) { return oc_reset(e); }
 int yta_hybridsort_capacity(yta_hybridsort *e, int *track_capacity, int *max_dets) {
-    YTA_CHECK(e && track_capacity && max_dets, YTA_ERR_INVALID, "null argument");
-    *track_capacity = e->CAP;
-    *max_dets = e->MAXD;
-    return YTA_OK;
+    return oc_capacity(e, track_capacity, max_dets);
 }
 
 int yta_hybridsort_update(yta_hybridsort *e, const double *dets, const int *det_offsets,
                           const float *feats, long long *next_id, double *out, int out_capacity,
                           int *out_offsets) {
     YTA_CHECK(e && det_offsets && out_offsets, YTA_ERR_INVALID, "null argument");
-    YTA_HIP(hipSetDevice(e->device));
-    const int S = e->S;
-    YTA_CHECK(det_offsets[0] == 0, YTA_ERR_INVALID, "det_offsets[0] must be 0");
-    int need_d = e->MAXD, need_c = e->CAP;
-    for (int s = 0; s < S; ++s) {
-        const int m = det_offsets[s + 1] - det_offsets[s];
-        YTA_CHECK(m >= 0, YTA_ERR_INVALID, "det_offsets must be non-decreasing");
-        need_d = std::max(need_d, m);
-        need_c = std::max(need_c, e->h_cnt[s].n_trk + m);
-    }
-    // every output row is a track matched to or born from one of this frame's detections, so
-    // det_offsets[S] rows always suffice; checked before anything moves (the frame is not consumed)
-    YTA_CHECK(out_capacity >= det_offsets[S], YTA_ERR_CAPACITY,
-              "out holds %d rows, the call needs det_offsets[S] = %d", out_capacity, det_offsets[S]);
-    if (need_d > e->MAXD || need_c > e->CAP) {
-        const int rc = hs_reserve(e, need_c > e->CAP ? std::max(need_c, 2 * e->CAP) : e->CAP,
-                                  need_d > e->MAXD ? std::max(need_d, 2 * e->MAXD) : e->MAXD);
-        if (rc) return rc;
-    }
-    const long long total = det_offsets[S];
+    long long total = 0;
+    int rc = oc_begin_frame(e, det_offsets, false, out_capacity, &total);   // asso_func < 4
+    if (rc) return rc;
     YTA_CHECK(total == 0 || (dets && feats), YTA_ERR_INVALID, "null dets / feats");
-    const int D = e->D;
-    if (total > e->det_cap) {
-        if (e->d_det_in) (void)hipFree(e->d_det_in);
-        if (e->h_dets) (void)hipHostFree(e->h_dets);
-        if (e->d_feat) (void)hipFree(e->d_feat);
-        if (e->h_feat) (void)hipHostFree(e->h_feat);
-        e->d_det_in = nullptr;
-        e->h_dets = nullptr;
-        e->d_feat = nullptr;
-        e->h_feat = nullptr;
-        e->det_cap = 0;
-        const long long cap = std::max<long long>(2 * total, 1024);
-        YTA_HIP(hipMalloc((void **)&e->d_det_in, sizeof(double) * 6 * cap));
-        YTA_HIP(hipHostMalloc((void **)&e->h_dets, sizeof(double) * 6 * cap, hipHostMallocDefault));
-        YTA_HIP(hipMalloc((void **)&e->d_feat, sizeof(float) * D * cap));
-        YTA_HIP(hipHostMalloc((void **)&e->h_feat, sizeof(float) * D * cap, hipHostMallocDefault));
-        e->det_cap = cap;
-    }
-    if (total) {
-        memcpy(e->h_dets, dets, sizeof(double) * 6 * total);
-        YTA_HIP(hipMemcpyAsync(e->d_det_in, e->h_dets, sizeof(double) * 6 * total,
-                               hipMemcpyHostToDevice, e->stream));
-        memcpy(e->h_feat, feats, sizeof(float) * D * total);
-        YTA_HIP(hipMemcpyAsync(e->d_feat, e->h_feat, sizeof(float) * D * total,
-                               hipMemcpyHostToDevice, e->stream));
-    }
-    memcpy(e->h_off, det_offsets, sizeof(int) * (S + 1));
-    YTA_HIP(hipMemcpyAsync(e->d_off, e->h_off, sizeof(int) * (S + 1), hipMemcpyHostToDevice,
-                           e->stream));
-    if (next_id) {
-        for (int s = 0; s < S; ++s) e->h_cnt[s].next_id = next_id[s];
-        YTA_HIP(hipMemcpy2DAsync(&e->a.cnt[0].next_id, sizeof(HsCounters), &e->h_cnt[0].next_id,
-                                 sizeof(HsCounters), sizeof(long long), S, hipMemcpyHostToDevice,
-                                 e->stream));
-    }
-    int rc = hs_launch(e, e->d_det_in, e->d_off, e->d_feat, e->a.out, nullptr);
+    rc = oc_stage_dets(e, dets, total);
+    if (!rc) rc = oc_grow_feats(e, total);
+    if (!rc && total)
+        rc = oc_stage(e, e->d_feat, e->h_feat, feats, sizeof(float) * e->D * total);
+    if (!rc) rc = oc_stage_offsets(e, det_offsets);
+    if (!rc) rc = oc_put_next_id(e, next_id);
+    if (!rc) rc = hs_launch(e, e->d_det_in, e->b.d_off, e->d_feat, e->b.a.out, nullptr);
     if (rc) return rc;
-    rc = hs_read_counters(e);
-    if (rc) return rc;
-    if (next_id)   // the device counters have advanced: hand them back even on an error below
-        for (int s = 0; s < S; ++s) next_id[s] = e->h_cnt[s].next_id;
-    rc = hs_check_errors(e);
-    if (rc) return rc;
-    long long rows = 0;
-    out_offsets[0] = 0;
-    for (int s = 0; s < S; ++s) {
-        rows += e->h_cnt[s].n_out;
-        out_offsets[s + 1] = (int)rows;
-    }
-    YTA_CHECK(rows <= out_capacity, YTA_ERR_CAPACITY, "output needs %lld rows > capacity %d", rows,
-              out_capacity);
-    YTA_CHECK(rows == 0 || out, YTA_ERR_INVALID, "null out");
-    for (int s = 0; s < S; ++s) {
-        const int n = e->h_cnt[s].n_out;
-        if (n)
-            YTA_HIP(hipMemcpyAsync(out + (long long)out_offsets[s] * 8,
-                                   e->a.out + (long long)s * e->CAP * 8, sizeof(double) * 8 * n,
-                                   hipMemcpyDeviceToHost, e->stream));
-    }
-    YTA_HIP(host_wait(e->stream));
-    return YTA_OK;
+    return oc_end_frame(e, next_id, out, out_capacity, out_offsets, ERR_INF_ROW, HS_INF_ROW_TEXT);
 }
 
 int yta_hybridsort_update_device(yta_hybridsort *e, const double *d_dets, const int *d_det_offsets,
@@ -1557,27 +1311,23 @@ int yta_hybridsort_update_device(yta_hybridsort *e, const double *d_dets, const 
     return hs_launch(e, d_dets, d_det_offsets, d_feats, d_out, d_out_counts);
 }
 
-int yta_hybridsort_sync(yta_hybridsort *e) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    const int rc = hs_read_counters(e);
-    if (rc) return rc;
-    return hs_check_errors(e);
-}
+int yta_hybridsort_sync(yta_hybridsort *e) { return oc_sync(e, ERR_INF_ROW, HS_INF_ROW_TEXT); }
 
 int yta_hybridsort_get_state(yta_hybridsort *e, int stream, int *n_tracks, long long *ints,
                              double *dbl, double *x, double *P, float *feat) {
     YTA_CHECK(e && n_tracks && ints && dbl && x && P, YTA_ERR_INVALID, "null argument");
     YTA_CHECK(stream >= 0 && stream < e->S, YTA_ERR_INVALID, "bad stream %d", stream);
     YTA_HIP(hipSetDevice(e->device));
-    const int rc = hs_read_counters(e);
+    const int rc = oc_read_counters(e);
     if (rc) return rc;
-    const HsCounters c = e->h_cnt[stream];
-    const long long tb = (long long)stream * e->CAP;
+    const HsCounters c = e->b.h_cnt[stream];
+    const HsArgs &a = e->b.a;
+    const long long tb = (long long)stream * a.CAP;
     std::vector<int> lst(c.n_trk);
-    std::vector<HsTrack> rec(e->CAP);
+    std::vector<HsTrack> rec(a.CAP);
     if (c.n_trk)
-        YTA_HIP(hipMemcpy(lst.data(), e->a.list + tb, sizeof(int) * c.n_trk, hipMemcpyDeviceToHost));
-    YTA_HIP(hipMemcpy(rec.data(), e->a.rec + tb, sizeof(HsTrack) * e->CAP, hipMemcpyDeviceToHost));
+        YTA_HIP(hipMemcpy(lst.data(), a.list + tb, sizeof(int) * c.n_trk, hipMemcpyDeviceToHost));
+    YTA_HIP(hipMemcpy(rec.data(), a.rec + tb, sizeof(HsTrack) * a.CAP, hipMemcpyDeviceToHost));
     for (int i = 0; i < c.n_trk; ++i) {
         const HsTrack &r = rec[lst[i]];
         long long *ii = ints + 6LL * i;
@@ -1602,7 +1352,7 @@ int yta_hybridsort_get_state(yta_hybridsort *e, int stream, int *n_tracks, long 
         }
         M[4 * 9 + 4] = r.kf.p[16];
         if (feat)
-            YTA_HIP(hipMemcpy(feat + (long long)i * e->D, e->a.feat + (tb + lst[i]) * e->D,
+            YTA_HIP(hipMemcpy(feat + (long long)i * e->D, a.feat + (tb + lst[i]) * e->D,
                               sizeof(float) * e->D, hipMemcpyDeviceToHost));
     }
     *n_tracks = c.n_trk;
@@ -1613,16 +1363,17 @@ int yta_hybridsort_classes(yta_hybridsort *e, int stream, double *cls, int cap, 
     YTA_CHECK(e && n && (cls || cap == 0), YTA_ERR_INVALID, "null argument");
     YTA_CHECK(stream >= 0 && stream < e->S, YTA_ERR_INVALID, "bad stream %d", stream);
     YTA_HIP(hipSetDevice(e->device));
-    const int rc = hs_read_counters(e);
+    const int rc = oc_read_counters(e);
     if (rc) return rc;
-    const int nt = e->h_cnt[stream].n_trk;
+    const int nt = e->b.h_cnt[stream].n_trk;
     YTA_CHECK(nt <= cap, YTA_ERR_CAPACITY, "%d trackers > capacity %d", nt, cap);
-    const long long tb = (long long)stream * e->CAP;
+    const HsArgs &a = e->b.a;
+    const long long tb = (long long)stream * a.CAP;
     std::vector<int> lst(nt);
     if (nt)
-        YTA_HIP(hipMemcpy(lst.data(), e->a.list + tb, sizeof(int) * nt, hipMemcpyDeviceToHost));
+        YTA_HIP(hipMemcpy(lst.data(), a.list + tb, sizeof(int) * nt, hipMemcpyDeviceToHost));
     for (int i = 0; i < nt; ++i)
-        YTA_HIP(hipMemcpy(cls + i, (const char *)(e->a.rec + tb + lst[i]) + offsetof(HsTrack, cls),
+        YTA_HIP(hipMemcpy(cls + i, (const char *)(a.rec + tb + lst[i]) + offsetof(HsTrack, cls),
                           sizeof(double), hipMemcpyDeviceToHost));
     *n = nt;
     return YTA_OK;
@@ -1630,11 +1381,11 @@ int yta_hybridsort_classes(yta_hybridsort *e, int stream, double *cls, int cap, 
 
 int yta_hybridsort_stats(yta_hybridsort *e, long long *stats) {
     YTA_CHECK(e && stats, YTA_ERR_INVALID, "null argument");
-    const int rc = hs_read_counters(e);
+    const int rc = oc_read_counters(e);
     if (rc) return rc;
     for (int k = 0; k < 8; ++k) stats[k] = 0;
     for (int s = 0; s < e->S; ++s) {
-        const HsCounters &c = e->h_cnt[s];
+        const HsCounters &c = e->b.h_cnt[s];
         const long long v[8] = {c.n_dets, c.n_high, c.n_trk, c.n_out, c.n_births, c.lap_calls,
                                 c.corrections, c.n_ema};
         for (int k = 0; k < 8; ++k) stats[k] += v[k];
@@ -1676,25 +1427,10 @@ int yta_kf9_run(int device, int n, int steps, const double *b0, const double *b,
 }
 
 int yta_hybridsort_lap_stats(yta_hybridsort *e, long long *stats, int n) {
-    YTA_CHECK(e && (stats || n <= 0), YTA_ERR_INVALID, "null argument");
-    const int rc = hs_read_counters(e);
-    if (rc) return rc;
-    long long v[YTA_LAP_STATS] = {};
-    for (int s = 0; s < e->S; ++s) {
-        const LapStats &l = e->h_cnt[s].ls;
-        v[0] += l.transposed;
-        v[1] += l.uncertified;
-        v[2] += l.replays;
-        v[3] += l.reduced;
-    }
-    for (int k = 0; k < n && k < YTA_LAP_STATS; ++k) stats[k] = v[k];
-    return YTA_OK;
+    return oc_lap_stats(e, stats, n);
 }
-
 int yta_hybridsort_hip_stream(yta_hybridsort *e, void **stream) {
-    YTA_CHECK(e && stream, YTA_ERR_INVALID, "null argument");
-    *stream = (void *)e->stream;
-    return YTA_OK;
+    return oc_hip_stream(e, stream);
 }
 
 #ifdef YTA_STAMPS
@@ -1721,49 +1457,27 @@ int yta_hs_debug_stamps_reset() {
 
 // ---- stream subsets (subset.hpp): the listed streams updated, every other stream untouched
 int yta_hybridsort_reset_stream(yta_hybridsort *e, int stream) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    YTA_CHECK(stream >= 0 && stream < e->S, YTA_ERR_INVALID, "stream %d outside 0..%d", stream,
-              e->S - 1);
-    YTA_HIP(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_hs_reset, dim3(1), dim3(256), 0, e->stream, e->a, stream);
-    YTA_HIP(hipGetLastError());
-    YTA_HIP(host_wait(e->stream));
-    return hs_read_counters(e);
+    return oc_reset_stream(e, stream);
 }
 
-int yta_hybridsort_update_device_masked(yta_hybridsort *e, const int *d_active, const double *d_dets, const int *d_det_offsets, const float *d_feats, double *d_out, int *d_out_counts) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    e->mask.req_dev = d_active;
-    const int rc = yta_hybridsort_update_device(e, d_dets, d_det_offsets, d_feats, d_out, d_out_counts);
-    e->mask.req_dev = nullptr;
-    return rc;
+int yta_hybridsort_update_device_masked(yta_hybridsort *e, const int *d_active,
+                                        const double *d_dets, const int *d_det_offsets,
+                                        const float *d_feats, double *d_out, int *d_out_counts) {
+    return oc_update_device_masked(e, d_active, [&] {
+        return yta_hybridsort_update_device(e, d_dets, d_det_offsets, d_feats, d_out,
+                                            d_out_counts);
+    });
 }
 
-int yta_hybridsort_update_streams(yta_hybridsort *e, int n_streams, const int *stream_ids, const double *dets, const int *det_offsets, const float *feats,
-                           long long *next_id, double *out, int out_capacity, int *out_offsets) {
-    YTA_CHECK(e && out_offsets, YTA_ERR_INVALID, "null argument");
-    YTA_HIP(hipSetDevice(e->device));
-    const int S = e->S;
-    std::vector<int> mask, off, full_oo(S + 1, 0);
-    int rc = subset_expand(S, n_streams, stream_ids, det_offsets, mask, off);
-    if (rc) return rc;
-    std::vector<long long> nid(S);
-    if (next_id) {   // the skipped streams keep their device counters: read them first
-        rc = hs_read_counters(e);
-        if (rc) return rc;
-        for (int s = 0; s < S; ++s) nid[s] = e->h_cnt[s].next_id;
-        for (int k = 0; k < n_streams; ++k) nid[stream_ids[k]] = next_id[k];
-    }
-
-    e->mask.req_host = mask.data();
-    rc = yta_hybridsort_update(e, dets, off.data(), feats, next_id ? nid.data() : nullptr, out,
-                        out_capacity, full_oo.data());
-    e->mask.req_host = nullptr;
-    if (next_id)
-        for (int k = 0; k < n_streams; ++k) next_id[k] = nid[stream_ids[k]];
-    if (rc) return rc;
-    subset_compact(n_streams, stream_ids, full_oo, out_offsets);
-    return YTA_OK;
+int yta_hybridsort_update_streams(yta_hybridsort *e, int n_streams, const int *stream_ids,
+                                  const double *dets, const int *det_offsets, const float *feats,
+                                  long long *next_id, double *out, int out_capacity,
+                                  int *out_offsets) {
+    return oc_update_streams(
+        e, n_streams, stream_ids, det_offsets, next_id, out_offsets,
+        [&](const std::vector<int> &, const int *off, long long *nid, int *full_oo) {
+            return yta_hybridsort_update(e, dets, off, feats, nid, out, out_capacity, full_oo);
+        });
 }
 
 }  // extern "C"

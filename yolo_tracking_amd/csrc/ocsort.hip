@@ -29,7 +29,7 @@
 
 #include "kf_ocsort.hpp"
 #include "ocsort_common.hpp"
-#include "subset.hpp"
+#include "oc_host.hpp"
 
 namespace yta {
 namespace {
@@ -670,50 +670,28 @@ __global__ void k_oc_reset(OcArgs a, int s0) {
 // ================================================================================== host engine
 using namespace yta;
 
-struct yta_ocsort {
-    int device = 0, S = 0, CAP = 0, MAXD = 0;
-    yta_ocsort_params prm{};
-    hipStream_t stream = nullptr;
-    std::vector<void *> allocs;
-    OcArgs a{};
-    double *h_dets = nullptr, *d_det_in = nullptr;
-    long long det_cap = 0;
-    int *h_off = nullptr, *d_off = nullptr, *h_wh = nullptr, *d_wh = nullptr;
-    OcCounters *h_cnt = nullptr;
-    size_t lds = 0;
-    StreamMask mask;   // stream-subset updates (subset.hpp)
+struct OcBuf : OcSized<OcArgs, OcCounters> {
+    int *h_wh = nullptr, *d_wh = nullptr;
 };
 
-namespace {
-
-template <typename T>
-int oc_dalloc(yta_ocsort *e, T **p, long long n) {
-    void *q = nullptr;
-    if (n <= 0) n = 1;
-    hipError_t err = hipMalloc(&q, sizeof(T) * (size_t)n);
-    if (err != hipSuccess) {
-        set_error("hipMalloc(%lld bytes) failed: %s", (long long)(sizeof(T) * n),
-                  hipGetErrorString(err));
-        return YTA_ERR_NOMEM;
+struct yta_ocsort : OcEngine<OcBuf, yta_ocsort_params> {   // the skeleton: oc_host.hpp
+    int alloc(int cap, int maxd, OcBuf &b) const;
+    std::vector<SlotCopy> slot_arrays(OcBuf &n, const OcBuf &o) const {
+        return {{n.a.rec, o.a.rec, sizeof(OcTrack)}, {n.a.list, o.a.list, sizeof(int)}};
     }
-    e->allocs.push_back(q);
-    *p = static_cast<T *>(q);
-    return YTA_OK;
-}
+    void launch_reset(int s0, int n) {
+        hipLaunchKernelGGL(k_oc_reset, dim3(n), dim3(256), 0, stream, b.a, s0);
+    }
+};
 
-#define OCALLOC(ptr, n)                      \
-    do {                                     \
-        int _rc = oc_dalloc(e, &(ptr), (n)); \
-        if (_rc) return _rc;                 \
-    } while (0)
-
-int oc_alloc(yta_ocsort *e) {
-    const long long S = e->S, CAP = e->CAP, MAXD = e->MAXD;
-    OcArgs &a = e->a;
-    const yta_ocsort_params &p = e->prm;
-    a.S = e->S;
-    a.CAP = e->CAP;
-    a.MAXD = e->MAXD;
+int yta_ocsort::alloc(int cap, int maxd, OcBuf &b) const {
+    const long long S = this->S, CAP = cap, MAXD = maxd;
+    std::vector<void *> &allocs = b.allocs;   // DALLOC
+    OcArgs &a = b.a;
+    const yta_ocsort_params &p = prm;
+    a.S = this->S;
+    a.CAP = cap;
+    a.MAXD = maxd;
     a.det_thresh = p.det_thresh;
     a.thr = p.asso_threshold;
     a.inertia = p.inertia;
@@ -722,42 +700,42 @@ int oc_alloc(yta_ocsort *e) {
     a.delta_t = p.delta_t;
     a.asso = p.asso_func;
     a.use_byte = p.use_byte;
-    OCALLOC(a.rec, S * CAP);
-    OCALLOC(a.list, S * CAP);
-    OCALLOC(a.free_list, S * CAP);
-    OCALLOC(a.cnt, S);
-    OCALLOC(a.hi_row, S * MAXD);
-    OCALLOC(a.lo_row, S * MAXD);
-    OCALLOC(a.cbox, S * CAP);
-    OCALLOC(a.cvel, S * CAP * 2);
-    OCALLOC(a.ckobs, S * CAP * 5);
-    OCALLOC(a.clast, S * CAP * 5);
-    OCALLOC(a.nan_flag, S * CAP);
+    DALLOC(a.rec, S * CAP);
+    DALLOC(a.list, S * CAP);
+    DALLOC(a.free_list, S * CAP);
+    DALLOC(a.cnt, S);
+    DALLOC(a.hi_row, S * MAXD);
+    DALLOC(a.lo_row, S * MAXD);
+    DALLOC(a.cbox, S * CAP);
+    DALLOC(a.cvel, S * CAP * 2);
+    DALLOC(a.ckobs, S * CAP * 5);
+    DALLOC(a.clast, S * CAP * 5);
+    DALLOC(a.nan_flag, S * CAP);
     const long long mat = std::max<long long>(MAXD * CAP, 4 * CAP);   // (mat2 doubles as a Box
-    OCALLOC(a.mat, S * mat);                                            //  scratch of CAP boxes)
-    OCALLOC(a.mat2, S * mat);
-    OCALLOC(a.rmatch, S * MAXD);
-    OCALLOC(a.pre_u, S * MAXD);
-    OCALLOC(a.pre_s2, S * MAXD);
-    OCALLOC(a.pre_x, S * MAXD);
-    OCALLOC(a.cmatched, S * CAP);
-    OCALLOC(a.udet, S * (MAXD + CAP));
-    OCALLOC(a.utrk, S * (MAXD + CAP));
-    OCALLOC(a.tmp, S * (MAXD + CAP));
-    OCALLOC(a.upd, S * CAP);
-    OCALLOC(a.out, S * CAP * 8);
+    DALLOC(a.mat, S * mat);                                            //  scratch of CAP boxes)
+    DALLOC(a.mat2, S * mat);
+    DALLOC(a.rmatch, S * MAXD);
+    DALLOC(a.pre_u, S * MAXD);
+    DALLOC(a.pre_s2, S * MAXD);
+    DALLOC(a.pre_x, S * MAXD);
+    DALLOC(a.cmatched, S * CAP);
+    DALLOC(a.udet, S * (MAXD + CAP));
+    DALLOC(a.utrk, S * (MAXD + CAP));
+    DALLOC(a.tmp, S * (MAXD + CAP));
+    DALLOC(a.upd, S * CAP);
+    DALLOC(a.out, S * CAP * 8);
     const long long n = std::max(CAP, MAXD);
     a.lap_ws_stride = oc_lap_ws_stride(n);
-    OCALLOC(a.lap_ws, S * a.lap_ws_stride);
+    DALLOC(a.lap_ws, S * a.lap_ws_stride);
     a.lap_csr = nullptr;
     a.lap_csr_stride = n >= LAPB_MIN_N && lap_sparse_on() ? (lap_csr_bytes(n) + 255) & ~255LL : 0;
-    if (a.lap_csr_stride) OCALLOC(a.lap_csr, S * a.lap_csr_stride);
-    e->lds = (size_t)oc_lds_bytes(CAP, MAXD);
-    OCALLOC(e->d_off, S + 1);
-    OCALLOC(e->d_wh, 2 * S);
-    YTA_HIP(hipHostMalloc((void **)&e->h_off, sizeof(int) * (S + 1), hipHostMallocDefault));
-    YTA_HIP(hipHostMalloc((void **)&e->h_wh, sizeof(int) * 2 * S, hipHostMallocDefault));
-    YTA_HIP(hipHostMalloc((void **)&e->h_cnt, sizeof(OcCounters) * S, hipHostMallocDefault));
+    if (a.lap_csr_stride) DALLOC(a.lap_csr, S * a.lap_csr_stride);
+    b.lds = (size_t)oc_lds_bytes(CAP, MAXD);
+    DALLOC(b.d_off, S + 1);
+    DALLOC(b.d_wh, 2 * S);
+    YTA_HIP(b.pin(&b.h_off, S + 1));
+    YTA_HIP(b.pin(&b.h_wh, 2 * S));
+    YTA_HIP(b.pin(&b.h_cnt, S));
     YTA_HIP(hipFuncSetAttribute((const void *)k_oc_lap, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)LAP_LDS_MAX));
     YTA_HIP(hipFuncSetAttribute((const void *)k_oc_assoc, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -765,19 +743,11 @@ int oc_alloc(yta_ocsort *e) {
     return YTA_OK;
 }
 
-void oc_release(yta_ocsort *e) {
-    for (void *p : e->allocs) (void)hipFree(p);
-    e->allocs.clear();
-    if (e->h_off) (void)hipHostFree(e->h_off);
-    if (e->h_wh) (void)hipHostFree(e->h_wh);
-    if (e->h_cnt) (void)hipHostFree(e->h_cnt);
-    e->h_off = e->h_wh = nullptr;
-    e->h_cnt = nullptr;
-}
+namespace {
 
 int oc_launch(yta_ocsort *e, const double *d_dets, const int *d_off, const int *d_wh, double *out,
               int *out_counts) {
-    OcArgs &a = e->a;
+    OcArgs &a = e->b.a;
     a.det_in = d_dets;
     a.det_off = d_off;
     a.img_wh = d_wh;
@@ -804,112 +774,8 @@ int oc_launch(yta_ocsort *e, const double *d_dets, const int *d_off, const int *
     hipLaunchKernelGGL(k_oc_lap, dim3(a.S), dim3(LAP_T), (size_t)lap_kernel_lds(a.CAP, a.MAXD),
                        e->stream, a);
     YTA_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_oc_assoc, dim3(a.S), dim3(OC_T), e->lds, e->stream, a);
+    hipLaunchKernelGGL(k_oc_assoc, dim3(a.S), dim3(OC_T), e->b.lds, e->stream, a);
     YTA_HIP(hipGetLastError());
-    return YTA_OK;
-}
-
-int oc_read_counters(yta_ocsort *e) {
-    YTA_HIP(hipMemcpyAsync(e->h_cnt, e->a.cnt, sizeof(OcCounters) * e->S, hipMemcpyDeviceToHost,
-                           e->stream));
-    YTA_HIP(host_wait(e->stream));
-    return YTA_OK;
-}
-
-int oc_check_errors(yta_ocsort *e) {
-    for (int s = 0; s < e->S; ++s) {
-        const int err = e->h_cnt[s].err;
-        if (err) {
-            set_error("stream %d: device error flags 0x%x (%s%s%s%s)", s, err,
-                      err & ERR_GIOU ? "giou enclosure not positive (iou.py:58 assert) " : "",
-                      err & ERR_SOLVER ? "assignment solver failure " : "",
-                      err & ERR_TRACK_CAPACITY ? "track capacity exceeded " : "",
-                      err & ERR_DET_CAPACITY ? "too many detections " : "");
-            return (err & (ERR_TRACK_CAPACITY | ERR_DET_CAPACITY)) ? YTA_ERR_CAPACITY
-                   : (err & ERR_GIOU)                              ? YTA_ERR_INVALID
-                                                                   : YTA_ERR_HIP;
-        }
-    }
-    return YTA_OK;
-}
-
-// Grow capacity (tracks per stream / detections per stream), keeping every stream's state.
-int oc_reserve(yta_ocsort *e, int cap, int maxd) {
-    if (cap <= e->CAP && maxd <= e->MAXD) return YTA_OK;
-    cap = std::max(cap, e->CAP);
-    maxd = std::max(maxd, e->MAXD);
-    YTA_HIP(host_wait(e->stream));
-    yta_ocsort *n = new (std::nothrow) yta_ocsort();
-    YTA_CHECK(n, YTA_ERR_NOMEM, "out of host memory");
-    n->device = e->device;
-    n->S = e->S;
-    n->CAP = cap;
-    n->MAXD = maxd;
-    n->prm = e->prm;
-    n->stream = e->stream;
-    int rc = oc_alloc(n);
-    const size_t S = e->S, oc = e->CAP, nc = cap;
-    auto copy2d = [&](void *dst, size_t dp, const void *src, size_t sp, size_t w) -> int {
-        YTA_HIP(hipMemcpy2DAsync(dst, dp, src, sp, w, S, hipMemcpyDeviceToDevice, e->stream));
-        return YTA_OK;
-    };
-    if (!rc) rc = copy2d(n->a.rec, nc * sizeof(OcTrack), e->a.rec, oc * sizeof(OcTrack),
-                         oc * sizeof(OcTrack));
-    if (!rc) rc = copy2d(n->a.list, nc * 4, e->a.list, oc * 4, oc * 4);
-    if (!rc) {
-        // free slots: the old free list, then the new slots [oc, nc) (popped from the end:
-        // written so the lowest new slot is used first after the old ones)
-        std::vector<int> fl(nc * S);
-        std::vector<int> old(oc * S);
-        std::vector<OcCounters> cnt(S);
-        hipError_t he = hipMemcpyAsync(old.data(), e->a.free_list, sizeof(int) * oc * S,
-                                       hipMemcpyDeviceToHost, e->stream);
-        if (he == hipSuccess)
-            he = hipMemcpyAsync(cnt.data(), e->a.cnt, sizeof(OcCounters) * S,
-                                hipMemcpyDeviceToHost, e->stream);
-        if (he == hipSuccess) he = host_wait(e->stream);
-        if (he != hipSuccess) {
-            set_error("reserve: %s", hipGetErrorString(he));
-            rc = YTA_ERR_HIP;
-        } else {
-            for (size_t s = 0; s < S; ++s) {
-                int k = 0;
-                for (int q = (int)nc - 1; q >= (int)oc; --q) fl[s * nc + k++] = q;
-                for (int q = 0; q < cnt[s].n_free; ++q) fl[s * nc + k++] = old[s * oc + q];
-                cnt[s].n_free = k;
-            }
-            he = hipMemcpy(n->a.free_list, fl.data(), sizeof(int) * nc * S, hipMemcpyHostToDevice);
-            if (he == hipSuccess)
-                he = hipMemcpy(n->a.cnt, cnt.data(), sizeof(OcCounters) * S,
-                               hipMemcpyHostToDevice);
-            if (he != hipSuccess) {
-                set_error("reserve: %s", hipGetErrorString(he));
-                rc = YTA_ERR_HIP;
-            }
-        }
-    }
-    if (rc) {
-        n->stream = nullptr;
-        oc_release(n);
-        delete n;
-        return rc;
-    }
-    memcpy(n->h_cnt, e->h_cnt, sizeof(OcCounters) * S);
-    oc_release(e);
-    e->CAP = n->CAP;
-    e->MAXD = n->MAXD;
-    e->allocs.swap(n->allocs);
-    e->a = n->a;
-    e->lds = n->lds;
-    e->h_off = n->h_off;
-    e->h_wh = n->h_wh;
-    e->h_cnt = n->h_cnt;
-    e->d_off = n->d_off;
-    e->d_wh = n->d_wh;
-    n->h_off = n->h_wh = nullptr;
-    n->h_cnt = nullptr;
-    n->stream = nullptr;
-    delete n;
     return YTA_OK;
 }
 
@@ -929,144 +795,31 @@ int yta_ocsort_create(int device, int n_streams, int track_capacity, int max_det
     YTA_CHECK(!(params->use_byte && params->asso_func == 4), YTA_ERR_INVALID,
               "use_byte with centroid: the reference calls centroid_batch without w, h "
               "(ocsort.py:292) and raises");
-    *engine = nullptr;
-    int rc = select_device(device);
-    if (rc) return rc;
-    yta_ocsort *e = new (std::nothrow) yta_ocsort();
-    YTA_CHECK(e, YTA_ERR_NOMEM, "out of host memory");
-    e->device = device;
-    e->S = n_streams;
-    e->CAP = track_capacity;
-    e->MAXD = max_dets;
-    e->prm = *params;
-    hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
-    if (he != hipSuccess) {
-        set_error("hipStreamCreate: %s", hipGetErrorString(he));
-        delete e;
-        return YTA_ERR_HIP;
-    }
-    rc = oc_alloc(e);
-    if (!rc) rc = yta_ocsort_reset(e);
-    if (rc) {
-        yta_ocsort_destroy(e);
-        return rc;
-    }
-    *engine = e;
-    return YTA_OK;
+    return oc_create(device, n_streams, track_capacity, max_dets, 0, params, engine);
 }
 
-int yta_ocsort_destroy(yta_ocsort *e) {
-    if (!e) return YTA_OK;
-    (void)hipSetDevice(e->device);
-    if (e->stream) (void)host_wait(e->stream);
-    oc_release(e);
-    e->mask.release();
-    if (e->h_dets) (void)hipHostFree(e->h_dets);
-    if (e->d_det_in) (void)hipFree(e->d_det_in);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
-    return YTA_OK;
-}
-
-int yta_ocsort_reset(yta_ocsort *e) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    YTA_HIP(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_oc_reset, dim3(e->S), dim3(256), 0, e->stream, e->a, 0);
-    YTA_HIP(hipGetLastError());
-    YTA_HIP(host_wait(e->stream));
-    memset(e->h_cnt, 0, sizeof(OcCounters) * e->S);
-    return YTA_OK;
-}
-
+int yta_ocsort_destroy(yta_ocsort *e) { return oc_destroy(e); }
+int yta_ocsort_reset(yta_ocsort *e) { return oc_reset(e); }
 int yta_ocsort_capacity(yta_ocsort *e, int *track_capacity, int *max_dets) {
-    YTA_CHECK(e && track_capacity && max_dets, YTA_ERR_INVALID, "null argument");
-    *track_capacity = e->CAP;
-    *max_dets = e->MAXD;
-    return YTA_OK;
+    return oc_capacity(e, track_capacity, max_dets);
 }
 
 int yta_ocsort_update(yta_ocsort *e, const double *dets, const int *det_offsets,
                       const int *img_wh, long long *next_id, double *out, int out_capacity,
                       int *out_offsets) {
     YTA_CHECK(e && det_offsets && out_offsets, YTA_ERR_INVALID, "null argument");
-    YTA_HIP(hipSetDevice(e->device));
-    const int S = e->S;
-    YTA_CHECK(det_offsets[0] == 0, YTA_ERR_INVALID, "det_offsets[0] must be 0");
-    YTA_CHECK(img_wh || e->prm.asso_func != 4, YTA_ERR_INVALID, "centroid needs img_wh");
-    int need_d = e->MAXD, need_c = e->CAP;
-    for (int s = 0; s < S; ++s) {
-        const int m = det_offsets[s + 1] - det_offsets[s];
-        YTA_CHECK(m >= 0, YTA_ERR_INVALID, "det_offsets must be non-decreasing");
-        need_d = std::max(need_d, m);
-        need_c = std::max(need_c, e->h_cnt[s].n_trk + m);
-    }
-    // every output row is a track matched to or born from one of this frame's detections, so
-    // det_offsets[S] rows always suffice; checked before anything moves (the frame is not consumed)
-    YTA_CHECK(out_capacity >= det_offsets[S], YTA_ERR_CAPACITY,
-              "out holds %d rows, the call needs det_offsets[S] = %d", out_capacity, det_offsets[S]);
-    if (need_d > e->MAXD || need_c > e->CAP) {
-        const int rc = oc_reserve(e, need_c > e->CAP ? std::max(need_c, 2 * e->CAP) : e->CAP,
-                                  need_d > e->MAXD ? std::max(need_d, 2 * e->MAXD) : e->MAXD);
-        if (rc) return rc;
-    }
-    const long long total = det_offsets[S];
+    long long total = 0;
+    int rc = oc_begin_frame(e, det_offsets, img_wh != nullptr, out_capacity, &total);
+    if (rc) return rc;
     YTA_CHECK(total == 0 || dets, YTA_ERR_INVALID, "null dets");
-    if (total > e->det_cap) {
-        if (e->d_det_in) (void)hipFree(e->d_det_in);
-        if (e->h_dets) (void)hipHostFree(e->h_dets);
-        e->d_det_in = nullptr;
-        e->h_dets = nullptr;
-        e->det_cap = 0;
-        const long long cap = std::max<long long>(2 * total, 1024);
-        YTA_HIP(hipMalloc((void **)&e->d_det_in, sizeof(double) * 6 * cap));
-        YTA_HIP(hipHostMalloc((void **)&e->h_dets, sizeof(double) * 6 * cap, hipHostMallocDefault));
-        e->det_cap = cap;
-    }
-    if (total) {
-        memcpy(e->h_dets, dets, sizeof(double) * 6 * total);
-        YTA_HIP(hipMemcpyAsync(e->d_det_in, e->h_dets, sizeof(double) * 6 * total,
-                               hipMemcpyHostToDevice, e->stream));
-    }
-    memcpy(e->h_off, det_offsets, sizeof(int) * (S + 1));
-    YTA_HIP(hipMemcpyAsync(e->d_off, e->h_off, sizeof(int) * (S + 1), hipMemcpyHostToDevice,
-                           e->stream));
-    if (img_wh) {
-        memcpy(e->h_wh, img_wh, sizeof(int) * 2 * S);
-        YTA_HIP(hipMemcpyAsync(e->d_wh, e->h_wh, sizeof(int) * 2 * S, hipMemcpyHostToDevice,
-                               e->stream));
-    }
-    if (next_id) {
-        for (int s = 0; s < S; ++s) e->h_cnt[s].next_id = next_id[s];
-        YTA_HIP(hipMemcpy2DAsync(&e->a.cnt[0].next_id, sizeof(OcCounters), &e->h_cnt[0].next_id,
-                                 sizeof(OcCounters), sizeof(long long), S, hipMemcpyHostToDevice,
-                                 e->stream));
-    }
-    int rc = oc_launch(e, e->d_det_in, e->d_off, img_wh ? e->d_wh : nullptr, e->a.out, nullptr);
+    rc = oc_stage_dets(e, dets, total);
+    if (!rc) rc = oc_stage_offsets(e, det_offsets);
+    if (!rc && img_wh) rc = oc_stage(e, e->b.d_wh, e->b.h_wh, img_wh, sizeof(int) * 2 * e->S);
+    if (!rc) rc = oc_put_next_id(e, next_id);
+    if (!rc) rc = oc_launch(e, e->d_det_in, e->b.d_off, img_wh ? e->b.d_wh : nullptr, e->b.a.out,
+                            nullptr);
     if (rc) return rc;
-    rc = oc_read_counters(e);
-    if (rc) return rc;
-    if (next_id)   // the device counters have advanced: hand them back even on an error below
-        for (int s = 0; s < S; ++s) next_id[s] = e->h_cnt[s].next_id;
-    rc = oc_check_errors(e);
-    if (rc) return rc;
-    long long rows = 0;
-    out_offsets[0] = 0;
-    for (int s = 0; s < S; ++s) {
-        rows += e->h_cnt[s].n_out;
-        out_offsets[s + 1] = (int)rows;
-    }
-    YTA_CHECK(rows <= out_capacity, YTA_ERR_CAPACITY, "output needs %lld rows > capacity %d", rows,
-              out_capacity);
-    YTA_CHECK(rows == 0 || out, YTA_ERR_INVALID, "null out");
-    for (int s = 0; s < S; ++s) {
-        const int n = e->h_cnt[s].n_out;
-        if (n)
-            YTA_HIP(hipMemcpyAsync(out + (long long)out_offsets[s] * 8,
-                                   e->a.out + (long long)s * e->CAP * 8, sizeof(double) * 8 * n,
-                                   hipMemcpyDeviceToHost, e->stream));
-    }
-    YTA_HIP(host_wait(e->stream));
-    return YTA_OK;
+    return oc_end_frame(e, next_id, out, out_capacity, out_offsets);
 }
 
 int yta_ocsort_update_device(yta_ocsort *e, const double *d_dets, const int *d_det_offsets,
@@ -1076,12 +829,7 @@ int yta_ocsort_update_device(yta_ocsort *e, const double *d_dets, const int *d_d
     return oc_launch(e, d_dets, d_det_offsets, d_img_wh, d_out, d_out_counts);
 }
 
-int yta_ocsort_sync(yta_ocsort *e) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    const int rc = oc_read_counters(e);
-    if (rc) return rc;
-    return oc_check_errors(e);
-}
+int yta_ocsort_sync(yta_ocsort *e) { return oc_sync(e); }
 
 int yta_ocsort_get_state(yta_ocsort *e, int stream, int *n_tracks, long long *ints, double *x,
                          double *P) {
@@ -1090,13 +838,14 @@ int yta_ocsort_get_state(yta_ocsort *e, int stream, int *n_tracks, long long *in
     YTA_HIP(hipSetDevice(e->device));
     const int rc = oc_read_counters(e);
     if (rc) return rc;
-    const OcCounters c = e->h_cnt[stream];
-    const long long tb = (long long)stream * e->CAP;
+    const OcCounters c = e->b.h_cnt[stream];
+    const OcArgs &a = e->b.a;
+    const long long tb = (long long)stream * a.CAP;
     std::vector<int> lst(c.n_trk);
-    std::vector<OcTrack> rec(e->CAP);
+    std::vector<OcTrack> rec(a.CAP);
     if (c.n_trk)
-        YTA_HIP(hipMemcpy(lst.data(), e->a.list + tb, sizeof(int) * c.n_trk, hipMemcpyDeviceToHost));
-    YTA_HIP(hipMemcpy(rec.data(), e->a.rec + tb, sizeof(OcTrack) * e->CAP, hipMemcpyDeviceToHost));
+        YTA_HIP(hipMemcpy(lst.data(), a.list + tb, sizeof(int) * c.n_trk, hipMemcpyDeviceToHost));
+    YTA_HIP(hipMemcpy(rec.data(), a.rec + tb, sizeof(OcTrack) * a.CAP, hipMemcpyDeviceToHost));
     for (int i = 0; i < c.n_trk; ++i) {
         const OcTrack &r = rec[lst[i]];
         long long *ii = ints + 7LL * i;
@@ -1131,7 +880,7 @@ int yta_ocsort_stats(yta_ocsort *e, long long *stats) {
     if (rc) return rc;
     for (int k = 0; k < 8; ++k) stats[k] = 0;
     for (int s = 0; s < e->S; ++s) {
-        const OcCounters &c = e->h_cnt[s];
+        const OcCounters &c = e->b.h_cnt[s];
         const long long v[8] = {c.n_dets, c.n_high, c.n_second, c.n_trk,
                                 c.n_out, c.n_births, c.lap_calls, c.fast_path};
         for (int k = 0; k < 8; ++k) stats[k] += v[k];
@@ -1140,26 +889,9 @@ int yta_ocsort_stats(yta_ocsort *e, long long *stats) {
 }
 
 int yta_ocsort_lap_stats(yta_ocsort *e, long long *stats, int n) {
-    YTA_CHECK(e && (stats || n <= 0), YTA_ERR_INVALID, "null argument");
-    const int rc = oc_read_counters(e);
-    if (rc) return rc;
-    long long v[YTA_LAP_STATS] = {};
-    for (int s = 0; s < e->S; ++s) {
-        const LapStats &l = e->h_cnt[s].ls;
-        v[0] += l.transposed;
-        v[1] += l.uncertified;
-        v[2] += l.replays;
-        v[3] += l.reduced;
-    }
-    for (int k = 0; k < n && k < YTA_LAP_STATS; ++k) stats[k] = v[k];
-    return YTA_OK;
+    return oc_lap_stats(e, stats, n);
 }
-
-int yta_ocsort_hip_stream(yta_ocsort *e, void **stream) {
-    YTA_CHECK(e && stream, YTA_ERR_INVALID, "null argument");
-    *stream = (void *)e->stream;
-    return YTA_OK;
-}
+int yta_ocsort_hip_stream(yta_ocsort *e, void **stream) { return oc_hip_stream(e, stream); }
 
 #ifdef YTA_STAMPS
 int yta_ocsort_debug_stamps(unsigned long long *out) {
@@ -1168,59 +900,29 @@ int yta_ocsort_debug_stamps(unsigned long long *out) {
 }
 #endif
 
-// Kalman KAT: n tracks run `steps` steps of predict + update from z[step][track] (4 values; a
-// NaN first value = missed update, i.e. update(None)); track i starts from z0[i].  Final x (7)
-// and full P (49) per track.
-int yta_kf7_run(int device, int n, int steps, const double *z0, const double *z, double *x_out,
-                double *P_out);
-
-
 // ---- stream subsets (subset.hpp): the listed streams updated, every other stream untouched
-int yta_ocsort_reset_stream(yta_ocsort *e, int stream) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    YTA_CHECK(stream >= 0 && stream < e->S, YTA_ERR_INVALID, "stream %d outside 0..%d", stream,
-              e->S - 1);
-    YTA_HIP(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_oc_reset, dim3(1), dim3(256), 0, e->stream, e->a, stream);
-    YTA_HIP(hipGetLastError());
-    YTA_HIP(host_wait(e->stream));
-    return oc_read_counters(e);
+int yta_ocsort_reset_stream(yta_ocsort *e, int stream) { return oc_reset_stream(e, stream); }
+
+int yta_ocsort_update_device_masked(yta_ocsort *e, const int *d_active, const double *d_dets,
+                                    const int *d_det_offsets, const int *d_img_wh, double *d_out,
+                                    int *d_out_counts) {
+    return oc_update_device_masked(e, d_active, [&] {
+        return yta_ocsort_update_device(e, d_dets, d_det_offsets, d_img_wh, d_out, d_out_counts);
+    });
 }
 
-int yta_ocsort_update_device_masked(yta_ocsort *e, const int *d_active, const double *d_dets, const int *d_det_offsets, const int *d_img_wh, double *d_out, int *d_out_counts) {
-    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
-    e->mask.req_dev = d_active;
-    const int rc = yta_ocsort_update_device(e, d_dets, d_det_offsets, d_img_wh, d_out, d_out_counts);
-    e->mask.req_dev = nullptr;
-    return rc;
-}
-
-int yta_ocsort_update_streams(yta_ocsort *e, int n_streams, const int *stream_ids, const double *dets, const int *det_offsets, const int *img_wh,
-                           long long *next_id, double *out, int out_capacity, int *out_offsets) {
-    YTA_CHECK(e && out_offsets, YTA_ERR_INVALID, "null argument");
-    YTA_HIP(hipSetDevice(e->device));
-    const int S = e->S;
-    std::vector<int> mask, off, full_oo(S + 1, 0);
-    int rc = subset_expand(S, n_streams, stream_ids, det_offsets, mask, off);
-    if (rc) return rc;
-    std::vector<long long> nid(S);
-    if (next_id) {   // the skipped streams keep their device counters: read them first
-        rc = oc_read_counters(e);
-        if (rc) return rc;
-        for (int s = 0; s < S; ++s) nid[s] = e->h_cnt[s].next_id;
-        for (int k = 0; k < n_streams; ++k) nid[stream_ids[k]] = next_id[k];
-    }
-    std::vector<int> wh;
-    if (img_wh) wh = subset_spread<int>(S, n_streams, stream_ids, img_wh, 2, 1);
-    e->mask.req_host = mask.data();
-    rc = yta_ocsort_update(e, dets, off.data(), img_wh ? wh.data() : nullptr, next_id ? nid.data() : nullptr, out,
-                        out_capacity, full_oo.data());
-    e->mask.req_host = nullptr;
-    if (next_id)
-        for (int k = 0; k < n_streams; ++k) next_id[k] = nid[stream_ids[k]];
-    if (rc) return rc;
-    subset_compact(n_streams, stream_ids, full_oo, out_offsets);
-    return YTA_OK;
+int yta_ocsort_update_streams(yta_ocsort *e, int n_streams, const int *stream_ids,
+                              const double *dets, const int *det_offsets, const int *img_wh,
+                              long long *next_id, double *out, int out_capacity,
+                              int *out_offsets) {
+    return oc_update_streams(
+        e, n_streams, stream_ids, det_offsets, next_id, out_offsets,
+        [&](const std::vector<int> &, const int *off, long long *nid, int *full_oo) {
+            std::vector<int> wh;
+            if (img_wh) wh = subset_spread<int>(e->S, n_streams, stream_ids, img_wh, 2, 1);
+            return yta_ocsort_update(e, dets, off, img_wh ? wh.data() : nullptr, nid, out,
+                                     out_capacity, full_oo);
+        });
 }
 
 }  // extern "C"
@@ -1269,6 +971,9 @@ __global__ void k_kf7_run(int n, int steps, const double *z0, const double *z, d
 }
 }  // namespace
 
+// Kalman KAT: n tracks run `steps` steps of predict + update from z[step][track] (4 values; a
+// NaN first value = missed update, i.e. update(None)); track i starts from z0[i].  Final x (7)
+// and full P (49) per track.
 extern "C" int yta_kf7_run(int device, int n, int steps, const double *z0, const double *z,
                            double *x_out, double *P_out) {
     YTA_CHECK(n >= 0 && steps >= 0, YTA_ERR_INVALID, "negative size");
