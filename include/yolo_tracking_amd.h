@@ -428,6 +428,27 @@ int yta_ocsort_update(yta_ocsort *engine, const double *dets, const int *det_off
 int yta_ocsort_update_device(yta_ocsort *engine, const double *d_dets, const int *d_det_offsets,
                              const int *d_img_wh, double *d_out, int *d_out_counts);
 int yta_ocsort_sync(yta_ocsort *engine);
+/* Tensor path of the OC-SORT family: yta_bytetrack_update_tensors' contract (stream order, d_dets
+ * / dtype / row_stride / det_counts / next_id / d_active in, d_rows / d_row_offsets /
+ * d_row_stream out, mixing with the synchronous entry points) on this engine; results equal
+ * yta_ocsort_update's bit for bit on the same values.  img_wh: S x (width, height) in HOST memory,
+ * copied during the call (needed by the centroid cost only, NULL otherwise; centroid without it
+ * is YTA_ERR_INVALID).  Capacity: max_dets follows det_counts; a stream's trackers after the
+ * frame are at most those alive after the newest tensor frame known to have run plus every
+ * detection enqueued since, and only a bound that does not fit waits for the engine's stream,
+ * reads the exact counters and grows the engine as yta_ocsort_update would, so the device never
+ * raises its capacity flags here.  Every argument is checked before anything is enqueued. */
+int yta_ocsort_update_tensors(yta_ocsort *engine, void *caller_stream, const void *d_dets,
+                              int dtype, long long row_stride, const int *det_counts,
+                              const int *img_wh, const int *d_active, const long long *next_id,
+                              double *d_rows, long long rows_capacity, int *d_row_offsets,
+                              int *d_row_stream);
+/* Accounting of the tensor path (writes min(n, 4) int64): frames enqueued; host_waits, the calls
+ * that blocked on the device; reserves, the times the engine grew; ingest_skipped, the frames
+ * whose float64 rows were read in place. */
+int yta_ocsort_tensor_stats(yta_ocsort *engine, long long *out, int n);
+/* The S per-stream ID counters as the device holds them (waits for the engine's stream). */
+int yta_ocsort_next_ids(yta_ocsort *engine, long long *next_id);
 /* Stream subsets (see yta_bytetrack_update_streams): the listed streams (ascending ids) updated,
  * every other stream left exactly as it was; per-stream arguments (dets, img_wh n x 2, next_id,
  * out_offsets n + 1) cover the listed streams in id order.  The device form takes an [S] mask on
@@ -511,6 +532,20 @@ int yta_deepocsort_update_device(yta_deepocsort *engine, const double *d_dets,
                                  const double *d_warps, const int *d_img_wh, double *d_out,
                                  int *d_out_counts);
 int yta_deepocsort_sync(yta_deepocsort *engine);
+/* Tensor path (see yta_ocsort_update_tensors).  d_feats: one feat_dim-wide float32 row per
+ * DETECTION row, feat_stride floats apart (>= feat_dim; read in place when equal, else gathered
+ * by one strided device copy; NULL with embedding_off); rows of detections at or below det_thresh
+ * are never read, as in yta_deepocsort_update_device.  d_warps: S x 6 float64 on the device or
+ * NULL for the identity; finite warps are the caller's responsibility. */
+int yta_deepocsort_update_tensors(yta_deepocsort *engine, void *caller_stream, const void *d_dets,
+                                  int dtype, long long row_stride, const int *det_counts,
+                                  const float *d_feats, long long feat_stride,
+                                  const double *d_warps, const int *img_wh, const int *d_active,
+                                  const long long *next_id, double *d_rows,
+                                  long long rows_capacity, int *d_row_offsets, int *d_row_stream);
+/* As yta_ocsort_tensor_stats / yta_ocsort_next_ids. */
+int yta_deepocsort_tensor_stats(yta_deepocsort *engine, long long *out, int n);
+int yta_deepocsort_next_ids(yta_deepocsort *engine, long long *next_id);
 /* Stream subsets and per-stream reset: as yta_ocsort_update_streams / _update_device_masked /
  * _reset_stream (deep_ocsort.py:308-347 for a fresh tracker). */
 int yta_deepocsort_update_streams(yta_deepocsort *engine, int n_streams, const int *stream_ids,
@@ -582,6 +617,17 @@ int yta_hybridsort_update_device(yta_hybridsort *engine, const double *d_dets,
                                  const int *d_det_offsets, const float *d_feats, double *d_out,
                                  int *d_out_counts);
 int yta_hybridsort_sync(yta_hybridsort *engine);
+/* Tensor path (see yta_ocsort_update_tensors; no image size: asso_func is never centroid).
+ * d_feats: one feat_dim-wide float32 row per detection row, feat_stride floats apart (>=
+ * feat_dim; read in place when equal, else gathered by one strided device copy). */
+int yta_hybridsort_update_tensors(yta_hybridsort *engine, void *caller_stream, const void *d_dets,
+                                  int dtype, long long row_stride, const int *det_counts,
+                                  const float *d_feats, long long feat_stride,
+                                  const int *d_active, const long long *next_id, double *d_rows,
+                                  long long rows_capacity, int *d_row_offsets, int *d_row_stream);
+/* As yta_ocsort_tensor_stats / yta_ocsort_next_ids. */
+int yta_hybridsort_tensor_stats(yta_hybridsort *engine, long long *out, int n);
+int yta_hybridsort_next_ids(yta_hybridsort *engine, long long *next_id);
 /* Stream subsets and per-stream reset: as yta_ocsort_update_streams / _update_device_masked /
  * _reset_stream (hybridsort.py:329-361 for a fresh tracker). */
 int yta_hybridsort_update_streams(yta_hybridsort *engine, int n_streams, const int *stream_ids,

@@ -5,6 +5,7 @@
     python tools/bench_tracker.py --tracker botsort [--n 1024] [--dim 512] [--streams 1]
     python tools/bench_tracker.py --tracker deepocsort [--n 2048] [--dim 512] [--streams 1]
     python tools/bench_tracker.py --tracker hybridsort [--n 4096] [--dim 512] [--streams 8]
+    python tools/bench_tracker.py --tracker ocsort --tensors [--repeats 3] [--out FILE.jsonl]
 
 A step = one update() frame of every stream (SURVEY.md §8(d) synthetic streams; OCSORT with
 ocsort.yaml parameters and no low-confidence detections, BoT-SORT with botsort.yaml parameters
@@ -71,6 +72,13 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--cpu-frames", type=int, default=None)
     p.add_argument("--seed", type=int, default=2000)
+    p.add_argument("--tensors", action="store_true",
+                   help="ocsort / deepocsort / hybridsort: time update_tensors beside the raw "
+                        "update_device loop (run_tensors) instead of the config's JSON line")
+    p.add_argument("--repeats", type=int, default=3, help="--tensors: runs of each leg")
+    p.add_argument("--cap-mult", type=int, default=2,
+                   help="--tensors: track_capacity / n of both legs' engines (2: the configs')")
+    p.add_argument("--out", default=None, help="--tensors: also append the JSON lines here")
     return p.parse_args(argv)
 
 
@@ -360,8 +368,141 @@ def run(args, cpu=None, seeds=None, barrier=None):
     return line
 
 
+def run_tensors(args):
+    """--tensors: update_tensors against the raw update_device loop (ocsort / deepocsort /
+    hybridsort), timed as tools/bench_tensors.py times ByteTrack: one engine of all S streams per
+    leg, fresh for every repeat; a pre-roll of --warmup frames, then --steps timed frames that end
+    in a wait for the device.  The tensor leg passes each frame's packed float64 rows (read in
+    place), its feature rows, the device warps and the image sizes, and gets packed rows, offsets
+    and row_stream tensors back; the raw leg leaves S * track_capacity unpacked rows in HBM.
+    Prints one JSON line per leg and repeat, then a summary with tensor / raw of the best runs."""
+    import torch
+    from yolo_tracking_amd import _lib
+    from yolo_tracking_amd.synth import SyntheticStream, make_frames
+    assert args.tracker != "botsort", "--tensors: BoT-SORT is measured by tools/bench_tensors.py"
+    S, PRE, K = args.streams, args.warmup, args.steps
+    F = PRE + K
+    N = args.n or DEFAULT_N[args.tracker]
+    oc = args.tracker == "ocsort"
+    D = 0 if oc else args.dim
+    kw_stream = dict(low_conf_frac=0.0) if oc else dict(emb_dim=D, low_conf_frac=0.0)
+    streams = [make_frames(N, F, args.seed + s, **kw_stream) for s in range(S)]
+    d_dets = torch.from_numpy(np.stack(
+        [np.concatenate([streams[s][f][0] for s in range(S)]) for f in range(F)])).cuda()
+    counts = [N] * S
+    d_off = torch.arange(0, (S + 1) * N, N, dtype=torch.int32).cuda()
+    d_feat = None
+    if D:
+        feats = np.zeros((F, S * N, D), np.float32)
+        for f in range(F):
+            for s in range(S):
+                e = streams[s][f][1]
+                feats[f, s * N:(s + 1) * N] = e / np.linalg.norm(e)
+        d_feat = torch.from_numpy(feats).cuda()
+        del feats
+    shape = SyntheticStream(N, args.seed, **kw_stream).img_shape
+    d_wh = torch.tensor([[shape[1], shape[0]]] * S, dtype=torch.int32).cuda()
+    d_warp = torch.tensor([CMC_AFFINE] * S, dtype=torch.float64).cuda()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+
+    def engine():
+        kw = dict(track_capacity=args.cap_mult * N, max_dets=N)
+        if oc:
+            from yolo_tracking_amd.trackers.ocsort import OCSortEngine
+            return OCSortEngine(S, **OCSORT_YAML, **kw)
+        if args.tracker == "deepocsort":
+            from yolo_tracking_amd.trackers.deepocsort import DeepOCSortEngine
+            return DeepOCSortEngine(S, feat_dim=D, **DEEPOCSORT_YAML, **kw)
+        from yolo_tracking_amd.trackers.hybridsort import HybridSortEngine
+        return HybridSortEngine(S, feat_dim=D, **HYBRIDSORT_YAML, **kw)
+
+    def timed(step, eng):
+        torch.cuda.synchronize()
+        for f in range(PRE):
+            step(f)
+        torch.cuda.synchronize()
+        eng.sync()
+        t0 = time.perf_counter()
+        for f in range(PRE, F):
+            step(f)
+        t1 = time.perf_counter()   # the host is done enqueueing; the device may not be
+        torch.cuda.synchronize()
+        eng.sync()
+        return time.perf_counter() - t0, 1e3 * (t1 - t0) / K
+
+    def raw_leg():
+        eng = engine()
+        cap, _ = eng.capacity()
+        d_out = torch.empty((S * cap, 8), dtype=torch.float64, device="cuda")
+        d_cnt = torch.zeros(S, dtype=torch.int32, device="cuda")
+        if oc:
+            fn = eng.lib.yta_ocsort_update_device
+            step = lambda f: _lib.check(fn(eng.handle, p(d_dets[f]), p(d_off), p(d_wh), p(d_out),
+                                           p(d_cnt)))
+        elif args.tracker == "deepocsort":
+            fn = eng.lib.yta_deepocsort_update_device
+            step = lambda f: _lib.check(fn(eng.handle, p(d_dets[f]), p(d_off), p(d_feat[f]),
+                                           p(d_warp), p(d_wh), p(d_out), p(d_cnt)))
+        else:
+            fn = eng.lib.yta_hybridsort_update_device
+            step = lambda f: _lib.check(fn(eng.handle, p(d_dets[f]), p(d_off), p(d_feat[f]),
+                                           p(d_out), p(d_cnt)))
+        el, enq = timed(step, eng)
+        rows = int(d_cnt.sum())
+        eng.close()
+        return el, dict(host_enqueue_ms_per_frame=enq, out_rows_last=rows)
+
+    def tensor_leg():
+        eng = engine()
+        keep = [None]
+        shapes = [shape] * S
+        if oc:
+            step = lambda f: keep.__setitem__(0, eng.update_tensors(
+                d_dets[f], img_shapes=shapes, counts=counts))
+        elif args.tracker == "deepocsort":
+            step = lambda f: keep.__setitem__(0, eng.update_tensors(
+                d_dets[f], d_feat[f], warps=d_warp, img_shapes=shapes, counts=counts))
+        else:
+            step = lambda f: keep.__setitem__(0, eng.update_tensors(
+                d_dets[f], d_feat[f], counts=counts))
+        el, enq = timed(step, eng)
+        st = eng.tensor_stats()
+        rows = int(keep[0][1][-1])
+        eng.close()
+        return el, dict(host_enqueue_ms_per_frame=enq, out_rows_last=rows, **st)
+
+    lines, best = [], {}
+
+    def emit(rec):
+        rec = dict(rec, tracker=args.tracker, streams=S, n=N, dim=D, cap_mult=args.cap_mult,
+                   preroll=PRE, steps=K)
+        lines.append(rec)
+        print(json.dumps(rec), flush=True)
+
+    for r in range(args.repeats):
+        for name, leg in (("raw_update_device", raw_leg), ("update_tensors", tensor_leg)):
+            el, extra = leg()
+            rate = S * K / el
+            emit(dict(leg=name, repeat=r, calls_per_s=rate, ms_per_frame=1e3 * el / K, **extra))
+            best[name] = max(best.get(name, 0.0), rate)
+    emit(dict(leg="summary", best_calls_per_s=best,
+              tensor_over_raw=best["update_tensors"] / best["raw_update_device"],
+              extra_us_per_frame=1e6 * S * (1 / best["update_tensors"]
+                                            - 1 / best["raw_update_device"])))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as fh:
+            for rec in lines:
+                fh.write(json.dumps(rec) + "\n")
+    return lines
+
+
 def main():
-    print(json.dumps(run(parse())))
+    args = parse()
+    if args.tensors:
+        run_tensors(args)
+        return
+    print(json.dumps(run(args)))
 
 
 if __name__ == "__main__":

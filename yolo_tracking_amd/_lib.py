@@ -144,6 +144,17 @@ _SIGS = {
     "yta_bytetrack_tensor_stats": ([_P, _P, _I], _I),
     "yta_botsort_update_tensors": ([_P, _P, _P, _I, _LL, _P, _P, _LL, _P, _P, _P, _P, _LL, _P, _P],
                                    _I),
+    "yta_ocsort_update_tensors": ([_P, _P, _P, _I, _LL, _P, _P, _P, _P, _P, _LL, _P, _P], _I),
+    "yta_ocsort_tensor_stats": ([_P, _P, _I], _I),
+    "yta_ocsort_next_ids": ([_P, _P], _I),
+    "yta_deepocsort_update_tensors": ([_P, _P, _P, _I, _LL, _P, _P, _LL, _P, _P, _P, _P, _P, _LL,
+                                       _P, _P], _I),
+    "yta_deepocsort_tensor_stats": ([_P, _P, _I], _I),
+    "yta_deepocsort_next_ids": ([_P, _P], _I),
+    "yta_hybridsort_update_tensors": ([_P, _P, _P, _I, _LL, _P, _P, _LL, _P, _P, _P, _LL, _P, _P],
+                                      _I),
+    "yta_hybridsort_tensor_stats": ([_P, _P, _I], _I),
+    "yta_hybridsort_next_ids": ([_P, _P], _I),
     "yta_selftest": ([_I], _I),
     "yta_apply_block_map": ([_I, _I, _P, _P], _I),
     "yta_botsort_create": ([_I, _I, _I, _I, _I, _P, _P], _I),

@@ -1267,6 +1267,7 @@ int yta_deepocsort::alloc(int cap, int maxd, DocBuf &b) const {
     DALLOC(a.ema_slot, S * (MAXD + CAP));
     DALLOC(a.ema_row, S * (MAXD + CAP));
     DALLOC(a.out, S * CAP * 8);
+    b.out_own = a.out;
     const long long n = std::max(CAP, MAXD);
     a.lap_ws_stride = oc_lap_ws_stride(n);
     a.arr_chip = MAXD >= ARR_CHIP_MIN_DETS;
@@ -1441,7 +1442,7 @@ int yta_deepocsort_update(yta_deepocsort *e, const double *dets, const int *det_
     if (!rc && warps) rc = oc_stage(e, b.d_warp, b.h_warp, warps, sizeof(double) * 6 * S);
     if (!rc) rc = oc_put_next_id(e, next_id);
     if (!rc) rc = doc_launch(e, e->d_det_in, b.d_off, e->d_feat, warps ? b.d_warp : nullptr,
-                             img_wh ? b.d_wh : nullptr, b.a.out, nullptr);
+                             img_wh ? b.d_wh : nullptr, b.out_own, nullptr);
     if (rc) return rc;
     return oc_end_frame(e, next_id, out, out_capacity, out_offsets);
 }
@@ -1457,6 +1458,29 @@ int yta_deepocsort_update_device(yta_deepocsort *e, const double *d_dets,
 }
 
 int yta_deepocsort_sync(yta_deepocsort *e) { return oc_sync(e); }
+
+int yta_deepocsort_update_tensors(yta_deepocsort *e, void *caller_stream, const void *d_dets,
+                                  int dtype, long long row_stride, const int *det_counts,
+                                  const float *d_feats, long long feat_stride,
+                                  const double *d_warps, const int *img_wh, const int *d_active,
+                                  const long long *next_id, double *d_rows,
+                                  long long rows_capacity, int *d_row_offsets,
+                                  int *d_row_stream) {
+    YTA_CHECK(!d_warps || (uintptr_t)d_warps % sizeof(double) == 0, YTA_ERR_INVALID,
+              "d_warps not aligned to float64");
+    return oc_update_tensors(
+        e, caller_stream, d_dets, dtype, row_stride, det_counts, d_feats, feat_stride, img_wh,
+        d_active, next_id, d_rows, rows_capacity, d_row_offsets, d_row_stream,
+        [&](const double *dets, const int *off, const float *feats, const int *wh) {
+            return doc_launch(e, dets, off, feats, d_warps, wh, e->b.out_own, nullptr);
+        });
+}
+int yta_deepocsort_tensor_stats(yta_deepocsort *e, long long *out, int n) {
+    return oc_tensor_stats(e, out, n);
+}
+int yta_deepocsort_next_ids(yta_deepocsort *e, long long *next_id) {
+    return oc_next_ids(e, next_id);
+}
 
 int yta_deepocsort_get_state(yta_deepocsort *e, int stream, int *n_tracks, long long *ints,
                              double *x, double *P, double *emb) {

@@ -1167,6 +1167,7 @@ int yta_hybridsort::alloc(int cap, int maxd, HsBuf &b) const {
     DALLOC(a.ema_slot, S * (MAXD + CAP));
     DALLOC(a.ema_row, S * (MAXD + CAP));
     DALLOC(a.out, S * CAP * 8);
+    b.out_own = a.out;
     const long long n = std::max(CAP, MAXD);
     a.lap_ws_stride = oc_lap_ws_stride(n);
     a.arr_chip = MAXD >= ARR_CHIP_MIN_DETS;
@@ -1300,7 +1301,7 @@ int yta_hybridsort_update(yta_hybridsort *e, const double *dets, const int *det_
         rc = oc_stage(e, e->d_feat, e->h_feat, feats, sizeof(float) * e->D * total);
     if (!rc) rc = oc_stage_offsets(e, det_offsets);
     if (!rc) rc = oc_put_next_id(e, next_id);
-    if (!rc) rc = hs_launch(e, e->d_det_in, e->b.d_off, e->d_feat, e->b.a.out, nullptr);
+    if (!rc) rc = hs_launch(e, e->d_det_in, e->b.d_off, e->d_feat, e->b.out_own, nullptr);
     if (rc) return rc;
     return oc_end_frame(e, next_id, out, out_capacity, out_offsets, ERR_INF_ROW, HS_INF_ROW_TEXT);
 }
@@ -1312,6 +1313,26 @@ int yta_hybridsort_update_device(yta_hybridsort *e, const double *d_dets, const 
 }
 
 int yta_hybridsort_sync(yta_hybridsort *e) { return oc_sync(e, ERR_INF_ROW, HS_INF_ROW_TEXT); }
+
+int yta_hybridsort_update_tensors(yta_hybridsort *e, void *caller_stream, const void *d_dets,
+                                  int dtype, long long row_stride, const int *det_counts,
+                                  const float *d_feats, long long feat_stride,
+                                  const int *d_active, const long long *next_id, double *d_rows,
+                                  long long rows_capacity, int *d_row_offsets,
+                                  int *d_row_stream) {
+    return oc_update_tensors(
+        e, caller_stream, d_dets, dtype, row_stride, det_counts, d_feats, feat_stride, nullptr,
+        d_active, next_id, d_rows, rows_capacity, d_row_offsets, d_row_stream,
+        [&](const double *dets, const int *off, const float *feats, const int *) {
+            return hs_launch(e, dets, off, feats, e->b.out_own, nullptr);
+        });
+}
+int yta_hybridsort_tensor_stats(yta_hybridsort *e, long long *out, int n) {
+    return oc_tensor_stats(e, out, n);
+}
+int yta_hybridsort_next_ids(yta_hybridsort *e, long long *next_id) {
+    return oc_next_ids(e, next_id);
+}
 
 int yta_hybridsort_get_state(yta_hybridsort *e, int stream, int *n_tracks, long long *ints,
                              double *dbl, double *x, double *P, float *feat) {

@@ -724,6 +724,7 @@ int yta_ocsort::alloc(int cap, int maxd, OcBuf &b) const {
     DALLOC(a.tmp, S * (MAXD + CAP));
     DALLOC(a.upd, S * CAP);
     DALLOC(a.out, S * CAP * 8);
+    b.out_own = a.out;
     const long long n = std::max(CAP, MAXD);
     a.lap_ws_stride = oc_lap_ws_stride(n);
     DALLOC(a.lap_ws, S * a.lap_ws_stride);
@@ -816,8 +817,8 @@ int yta_ocsort_update(yta_ocsort *e, const double *dets, const int *det_offsets,
     if (!rc) rc = oc_stage_offsets(e, det_offsets);
     if (!rc && img_wh) rc = oc_stage(e, e->b.d_wh, e->b.h_wh, img_wh, sizeof(int) * 2 * e->S);
     if (!rc) rc = oc_put_next_id(e, next_id);
-    if (!rc) rc = oc_launch(e, e->d_det_in, e->b.d_off, img_wh ? e->b.d_wh : nullptr, e->b.a.out,
-                            nullptr);
+    if (!rc) rc = oc_launch(e, e->d_det_in, e->b.d_off, img_wh ? e->b.d_wh : nullptr,
+                            e->b.out_own, nullptr);
     if (rc) return rc;
     return oc_end_frame(e, next_id, out, out_capacity, out_offsets);
 }
@@ -830,6 +831,22 @@ int yta_ocsort_update_device(yta_ocsort *e, const double *d_dets, const int *d_d
 }
 
 int yta_ocsort_sync(yta_ocsort *e) { return oc_sync(e); }
+
+int yta_ocsort_update_tensors(yta_ocsort *e, void *caller_stream, const void *d_dets, int dtype,
+                              long long row_stride, const int *det_counts, const int *img_wh,
+                              const int *d_active, const long long *next_id, double *d_rows,
+                              long long rows_capacity, int *d_row_offsets, int *d_row_stream) {
+    return oc_update_tensors(
+        e, caller_stream, d_dets, dtype, row_stride, det_counts, nullptr, 0, img_wh, d_active,
+        next_id, d_rows, rows_capacity, d_row_offsets, d_row_stream,
+        [&](const double *dets, const int *off, const float *, const int *wh) {
+            return oc_launch(e, dets, off, wh, e->b.out_own, nullptr);
+        });
+}
+int yta_ocsort_tensor_stats(yta_ocsort *e, long long *out, int n) {
+    return oc_tensor_stats(e, out, n);
+}
+int yta_ocsort_next_ids(yta_ocsort *e, long long *next_id) { return oc_next_ids(e, next_id); }
 
 int yta_ocsort_get_state(yta_ocsort *e, int stream, int *n_tracks, long long *ints, double *x,
                          double *P) {

@@ -1,4 +1,5 @@
-"""Plumbing of the tensor path (yta_bytetrack_update_tensors / yta_botsort_update_tensors): checks
+"""Plumbing of the tensor path (yta_bytetrack_update_tensors / yta_botsort_update_tensors and the
+OC-SORT family's yta_ocsort / yta_deepocsort / yta_hybridsort _update_tensors): checks
 the caller's device tensors, lays them out as the C ABI wants them and allocates the outputs.
 Everything here is host-side bookkeeping or a torch call on the caller's stream; no value is read
 back from the device.  Anything wrong raises ValueError before a single launch.
@@ -69,7 +70,8 @@ def _pack(torch, rows, min_stride):
 class TensorFrame:
     """One frame's checked inputs and fresh outputs, ready for the C call."""
 
-    def __init__(self, engine, dets, counts, active, next_id, stream, feats=None, warps=None):
+    def __init__(self, engine, dets, counts, active, next_id, stream, feats=None, warps=None,
+                 img_shapes=None):
         import torch
         self.torch = torch
         S, dev = engine.n_streams, engine.device
@@ -77,6 +79,14 @@ class TensorFrame:
         # ---- checks first: nothing is allocated or enqueued for a frame that is refused
         dets, self.counts = _rows(torch, dets, counts, S, "dets", dev, 6, tuple(codes))
         total = int(self.counts.sum())
+        self.wh = None   # S x (width, height), host (the OC-SORT family's centroid cost)
+        if img_shapes is not None:
+            if len(img_shapes) != S:
+                raise ValueError(f"img_shapes: {len(img_shapes)} shapes for {S} streams")
+            self.wh = np.ascontiguousarray([[int(sh[1]), int(sh[0])] for sh in img_shapes],
+                                           dtype=np.int32)
+        elif getattr(engine, "asso_func", None) == "centroid":
+            raise ValueError("img_shapes: the centroid cost needs the image sizes")
         D = getattr(engine, "feat_dim", 0)
         if D:
             if feats is None:
@@ -142,3 +152,31 @@ class TensorFrame:
 
     def result(self):
         return self.rows, self.offsets, self.row_stream
+
+
+class TensorPath:
+    """update_tensors' companions for the OC-SORT family's engines (`_abi` names the C prefix:
+    yta_<_abi>_tensor_stats / _next_ids / _sync)."""
+    _abi = None
+
+    def _call(self, name, *args):
+        _lib.check(getattr(self.lib, f"yta_{self._abi}_{name}")(self._h, *args))
+
+    def tensor_stats(self):
+        """Accounting of update_tensors: frames enqueued, calls that blocked on the device,
+        engine growths, float64 frames read in place."""
+        names = ["frames", "host_waits", "reserves", "ingest_skipped"]
+        buf = (ctypes.c_longlong * len(names))()
+        self._call("tensor_stats", buf, len(names))
+        return {k: int(buf[i]) for i, k in enumerate(names)}
+
+    def next_ids(self):
+        """The S per-stream ID counters on the device (waits for the engine's stream)."""
+        nid = np.zeros(self.n_streams, dtype=np.int64)
+        self._call("next_ids", _lib.ptr(nid))
+        return nid
+
+    def sync(self):
+        """Wait for the engine's stream; raises if a frame since the last wait set a device
+        error flag."""
+        self._call("sync")

@@ -14,11 +14,13 @@ per-detection embeddings.  The camera warp (:391 cmc.apply) comes from SparseOpt
 apply(img, dets) -> 2x3 warp) replaces it.
 """
 import ctypes
+import inspect
 
 import numpy as np
 
 from .. import _lib
 from ._streams import StreamSubset
+from ._tensors import TensorFrame, TensorPath, is_cuda_tensor
 from ..appearance import build_reid
 from ..motion.cmc import default_cmc
 
@@ -29,8 +31,9 @@ class KalmanBoxTracker:
     count = 1
 
 
-class DeepOCSortEngine(StreamSubset):
+class DeepOCSortEngine(StreamSubset, TensorPath):
     """S independent DeepOCSORT streams sharing one device engine."""
+    _abi = "deepocsort"
 
     def __init__(self, n_streams=1, feat_dim=512, det_thresh=0.3, max_age=30, min_hits=3,
                  iou_threshold=0.3, delta_t=3, asso_func="iou", inertia=0.2,
@@ -41,6 +44,7 @@ class DeepOCSortEngine(StreamSubset):
         self.lib = _lib.load_library()
         self.n_streams = int(n_streams)
         self.device = _lib.parse_device(device)
+        self.asso_func = asso_func
         self.det_thresh = float(det_thresh)
         self.embedding_off = bool(embedding_off)
         self.feat_dim = 0 if embedding_off else int(feat_dim)
@@ -177,6 +181,35 @@ class DeepOCSortEngine(StreamSubset):
         o = self._out_off
         return [self._out[o[s]:o[s + 1]].copy() for s in range(self.n_streams)]
 
+    def update_tensors(self, dets, feats=None, warps=None, img_shapes=None, counts=None,
+                       active=None, next_id=None, stream=None):
+        """Stream-ordered update from device tensors to device tensors
+        (yta_deepocsort_update_tensors): nothing crosses the link and nothing is waited for.
+        feats: one float32 feat_dim-wide row per DETECTION row (a list of S (M_s, D) CUDA tensors
+        or one (total, D) tensor; None with embedding_off); only the rows of detections with
+        conf > det_thresh are read, the others may hold anything.  warps: optional (S, 2, 3)
+        float64 CUDA tensor (or host array, copied on the stream); non-finite entries are the
+        caller's responsibility here, since the host never sees a device tensor's values.
+        dets: a list of S CUDA tensors (M_s, 6), or one (total, 6) tensor (a column slice of a
+        wider tensor is passed with its row stride) with `counts`, the S per-stream row counts
+        (host ints); float64, float32 or float16, promoted exactly.  img_shapes: S image shapes
+        (h, w, ...) or None (the centroid cost needs them).  active: optional (S,) integer / bool
+        CUDA tensor, nonzero = update that stream.  next_id: optional host int64 (S,) counters
+        written before the frame (not updated: read next_ids() after a synchronisation).  stream:
+        the torch stream the inputs were produced on and the outputs are consumed on (default: the
+        current one).
+        Returns (rows (total, 8) float64, offsets (S + 1,) int32, row_stream (total,) int32) on
+        the engine's device: stream s's rows are rows[offsets[s]:offsets[s + 1]], row_stream[r] is
+        row r's stream and -1 from offsets[S] on.  Results equal update()'s bit for bit.
+        Raises ValueError, before anything is enqueued, for tensors on another device or of the
+        wrong shape or dtype."""
+        f = TensorFrame(self, dets, counts, active, next_id, stream, feats=feats, warps=warps,
+                        img_shapes=img_shapes)
+        _lib.check(self.lib.yta_deepocsort_update_tensors(
+            self._h, *f.common_head(), f._p(f.feats), int(f.feat_stride), f._p(f.warps),
+            _lib.ptr(f.wh), *f.common_tail()))
+        return f.result()
+
     def state(self, stream=0):
         """Trackers of one stream in list order: id, age, hits, hit_streak, time_since_update,
         observed, frozen; Kalman x (8), P (8x8) and the float64 embedding."""
@@ -253,7 +286,67 @@ class DeepOCSort:
             self._engine.update([np.zeros((0, 6))])   # they only advanced frame_count
         self._empty_frames = 0
 
+    def _update_tensor(self, dets, img, embs):
+        """update() for a CUDA tensor of detections (embs, when given, a CUDA tensor with one row
+        per detection): the embeddings and the rows stay on the device.  Only the kept boxes go
+        to the host, for the crops and the camera-motion estimate, which take host frames.  One
+        wait per call, to learn K and to keep the process-global KalmanBoxTracker.count."""
+        import torch
+        assert isinstance(img, np.ndarray), \
+            f"Unsupported 'img' input type '{type(img)}', valid format is np.ndarray"
+        assert dets.dim() == 2, "Unsupported 'dets' dimensions, valid number of dimensions is two"
+        assert dets.shape[1] == 6, "Unsupported 'dets' 2nd dimension lenght, valid lenghts is 6"
+        self.frame_count += 1
+        # compared as float64, like the engine and the ndarray path (:378-379)
+        keep = dets[:, 4].double() > self.det_thresh
+        need_boxes = (not self.embedding_off and embs is None) or \
+            (not self.cmc_off and self.cmc is not None)
+        kept_rows = dets[keep].double().cpu().numpy() if need_boxes else None
+        n_kept = len(kept_rows) if need_boxes else int(keep.sum())
+        feats = None
+        if not self.embedding_off and n_kept:                        # :383-387
+            if embs is not None:
+                if not is_cuda_tensor(embs) or embs.dim() != 2 or len(embs) != len(dets):
+                    raise ValueError("embs: with tensor dets, a CUDA tensor with one row per "
+                                     "detection is needed")
+                feats = embs.float()
+            else:
+                if self.model is None:
+                    raise RuntimeError(
+                        "DeepOCSort needs a ReID producer: pass reid=<object with "
+                        "get_features(xyxys, img)> or update(dets, img, embs=...)")
+                # ReIDDetectMultiBackend keeps them in HBM; a producer without as_tensor hands
+                # NumPy rows, which are uploaded
+                if "as_tensor" in inspect.signature(self.model.get_features).parameters:
+                    f = self.model.get_features(kept_rows[:, 0:4], img, as_tensor=True).float()
+                else:
+                    f = torch.from_numpy(np.asarray(self.model.get_features(
+                        kept_rows[:, 0:4], img), np.float32)).to(dets.device)
+                feats = torch.zeros((len(dets), f.shape[1]), dtype=torch.float32,
+                                    device=dets.device)
+                feats[keep] = f
+            if self._engine is None:
+                self._make_engine(feats.shape[1])
+        warp = None
+        if not self.cmc_off and self.cmc is not None:                # :390-393
+            warp = np.asarray(self.cmc.apply(img, kept_rows[:, :4]), dtype=np.float64)[None]
+        if self._engine is None:                                     # no kept detection yet
+            self._empty_frames += 1
+            return dets.new_zeros((0, 8), dtype=torch.float64)
+        if feats is None and self._engine.feat_dim:   # no kept row: none is read
+            feats = torch.zeros((len(dets), self._engine.feat_dim), dtype=torch.float32,
+                                device=dets.device)
+        self._nid[0] = KalmanBoxTracker.count
+        rows, off, _ = self._engine.update_tensors([dets], feats, warps=warp,
+                                                   img_shapes=[img.shape], next_id=self._nid)
+        KalmanBoxTracker.count = int(self._engine.next_ids()[0])   # waits: the frame has run
+        return rows[:int(off[1])]
+
     def update(self, dets, img, embs=None):
+        """dets: np.ndarray (N, 6) as the reference; a CUDA tensor (N, 6) is taken where it is
+        (embs then a CUDA tensor too) and the (K, 8) result is then a CUDA tensor."""
+        if is_cuda_tensor(dets):
+            return self._update_tensor(dets, img, embs)
         assert isinstance(dets, np.ndarray), \
             f"Unsupported 'dets' input type '{type(dets)}', valid format is np.ndarray"
         assert isinstance(img, np.ndarray), \

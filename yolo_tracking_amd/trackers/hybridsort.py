@@ -21,6 +21,7 @@ import numpy as np
 
 from .. import _lib
 from ._streams import StreamSubset
+from ._tensors import TensorFrame, TensorPath
 from ..appearance import build_reid
 
 
@@ -30,9 +31,10 @@ class KalmanBoxTracker:
     count = 0
 
 
-class HybridSortEngine(StreamSubset):
+class HybridSortEngine(StreamSubset, TensorPath):
     """S independent HybridSORT streams sharing one device engine; one update() = one
     undecorated HybridSORT.update call per stream."""
+    _abi = "hybridsort"
 
     def __init__(self, n_streams=1, feat_dim=512, det_thresh=0.0, max_age=30, min_hits=3,
                  iou_threshold=0.3, delta_t=3, asso_func="iou", inertia=0.2, device=0,
@@ -153,6 +155,18 @@ class HybridSortEngine(StreamSubset):
         o = self._out_off
         return [self._out[o[s]:o[s + 1]].copy() for s in range(self.n_streams)]
 
+    def update_tensors(self, dets, feats, counts=None, active=None, next_id=None, stream=None):
+        """Stream-ordered update from device tensors to device tensors
+        (yta_hybridsort_update_tensors): nothing crosses the link and nothing is waited for.
+        feats: one float32 feat_dim-wide row per detection row (a list of S (M_s, D) CUDA tensors
+        or one (total, D) tensor, a column slice included).  dets, counts, active, next_id,
+        stream and the returned (rows, offsets, row_stream) as OCSortEngine.update_tensors;
+        results equal update()'s bit for bit.  Raises ValueError before anything is enqueued."""
+        f = TensorFrame(self, dets, counts, active, next_id, stream, feats=feats)
+        _lib.check(self.lib.yta_hybridsort_update_tensors(
+            self._h, *f.common_head(), f._p(f.feats), int(f.feat_stride), *f.common_tail()))
+        return f.result()
+
     def classes(self, stream=0):
         """The cls of every live tracker in list order (PerClassDecorator's active classes)."""
         cap, _ = self.capacity()
@@ -186,7 +200,9 @@ class HybridSORT:
 
     reid_weights / half name the reference's ReID model, which is outside the hot path: pass
     `reid=` (an object with get_features(xyxys, img) -> (n, D) float32) or give
-    `update(..., embs=...)` the get_features rows of every input detection.
+    `update(..., embs=...)` the get_features rows of every input detection.  update() takes NumPy
+    only: the per-class replay splits the call by class on the host
+    (HybridSortEngine.update_tensors is the device-tensor entry point).
     """
 
     def __init__(self, reid_weights=None, device=0, half=False, det_thresh=0.0, max_age=30,

@@ -12,6 +12,7 @@ import numpy as np
 
 from .. import _lib
 from ._streams import StreamSubset
+from ._tensors import TensorFrame, TensorPath, is_cuda_tensor
 
 
 class KalmanBoxTracker:
@@ -20,8 +21,9 @@ class KalmanBoxTracker:
     count = 0
 
 
-class OCSortEngine(StreamSubset):
+class OCSortEngine(StreamSubset, TensorPath):
     """S independent OCSORT streams sharing one device engine."""
+    _abi = "ocsort"
 
     def __init__(self, n_streams=1, det_thresh=0.2, max_age=30, min_hits=3, asso_threshold=0.3,
                  delta_t=3, asso_func="iou", inertia=0.2, use_byte=False, device=0,
@@ -134,6 +136,28 @@ class OCSortEngine(StreamSubset):
         o = self._out_off
         return [self._out[o[s]:o[s + 1]].copy() for s in range(self.n_streams)]
 
+    def update_tensors(self, dets, img_shapes=None, counts=None, active=None, next_id=None,
+                       stream=None):
+        """Stream-ordered update from device tensors to device tensors
+        (yta_ocsort_update_tensors): nothing crosses the link and nothing is waited for.
+        dets: a list of S CUDA tensors (M_s, 6), or one (total, 6) tensor (a column slice of a
+        wider tensor is passed with its row stride) with `counts`, the S per-stream row counts
+        (host ints); float64, float32 or float16, promoted exactly.  img_shapes: S image shapes
+        (h, w, ...) or None (the centroid cost needs them).  active: optional (S,) integer / bool
+        CUDA tensor, nonzero = update that stream.  next_id: optional host int64 (S,) counters
+        written before the frame (not updated: read next_ids() after a synchronisation).  stream:
+        the torch stream the inputs were produced on and the outputs are consumed on (default: the
+        current one).
+        Returns (rows (total, 8) float64, offsets (S + 1,) int32, row_stream (total,) int32) on
+        the engine's device: stream s's rows are rows[offsets[s]:offsets[s + 1]], row_stream[r] is
+        row r's stream and -1 from offsets[S] on.  Results equal update()'s bit for bit.
+        Raises ValueError, before anything is enqueued, for tensors on another device or of the
+        wrong shape or dtype."""
+        f = TensorFrame(self, dets, counts, active, next_id, stream, img_shapes=img_shapes)
+        _lib.check(self.lib.yta_ocsort_update_tensors(self._h, *f.common_head(), _lib.ptr(f.wh),
+                                                      *f.common_tail()))
+        return f.result()
+
     def state(self, stream=0):
         """Trackers of one stream in list order: id, age, hits, hit_streak, time_since_update,
         observed, saved; Kalman x (7) and P (7x7)."""
@@ -170,7 +194,22 @@ class OCSort:
                                     asso_func, inertia, use_byte, device=device)
         self._nid = np.zeros(1, dtype=np.int64)
 
+    def _update_tensor(self, dets, img):
+        """update() for a CUDA tensor of detections: the rows stay on the device.  One wait per
+        call, to learn K and to keep the process-global KalmanBoxTracker.count."""
+        assert dets.dim() == 2, "Unsupported 'dets' dimensions, valid number of dimensions is two"
+        assert dets.shape[1] == 6, "Unsupported 'dets' 2nd dimension lenght, valid lenghts is 6"
+        self.frame_count += 1
+        self._nid[0] = KalmanBoxTracker.count
+        rows, off, _ = self._engine.update_tensors([dets], [img.shape], next_id=self._nid)
+        KalmanBoxTracker.count = int(self._engine.next_ids()[0])   # waits: the frame has run
+        return rows[:int(off[1])]
+
     def update(self, dets, img):
+        """dets: np.ndarray (N, 6) as the reference; a CUDA tensor (N, 6) is taken where it is
+        and the (K, 8) result is then a CUDA tensor too."""
+        if is_cuda_tensor(dets):
+            return self._update_tensor(dets, img)
         assert isinstance(dets, np.ndarray), \
             f"Unsupported 'dets' input format '{type(dets)}', valid format is np.ndarray"
         assert len(dets.shape) == 2, \
