@@ -711,6 +711,18 @@ int yta_reid_preprocess_device(const uint8_t *d_imgs, const long long *d_img_off
                                const int *d_img_hw, const double *d_xyxys, const int *d_box_img,
                                int n, int out_h, int out_w, int half, void *d_out, int *d_n_empty,
                                void *stream);
+/* Tensor form: the stateless sibling of yta_reid_preprocess_device for frames that are device
+ * tensors, run on `stream`.  d_frames: a device array of the images' first-pixel addresses (any
+ * number of separately allocated, pitched or offset views); d_img_hw as above; d_img_pitch: a
+ * device array of the bytes between rows of each image (>= 3 w and below 2^31, no alignment
+ * requirement; the pixel stride is 3).  d_boxes: rows x1 y1 x2 y2 of dtype (YTA_F64 / YTA_F32 / YTA_F16), row_stride
+ * (>= 4) elements apart, aligned to the element size only; values are promoted to float64, which
+ * is exact, so the crops equal yta_reid_preprocess's on the promoted boxes.  Box values never reach
+ * the host: an empty crop is zero-filled and counted into *d_n_empty, as in the device form. */
+int yta_reid_preprocess_tensors(const void *const *d_frames, const int *d_img_hw,
+                                const long long *d_img_pitch, const void *d_boxes, int dtype,
+                                long long row_stride, const int *d_box_img, int n, int out_h,
+                                int out_w, int half, void *d_out, int *d_n_empty, void *stream);
 /* get_features (reid_multibackend.py:310): feats[0..count) /= ||feats||_2 over the whole batch,
  * float32 in place (sum of squares accumulated in float64).  Synchronous, host buffer. */
 int yta_reid_normalize(int device, float *feats, long long count);
@@ -748,6 +760,32 @@ int yta_sof_apply(yta_sof *engine, const uint8_t *frames, const long long *frame
 int yta_sof_apply_device(yta_sof *engine, const uint8_t *d_frames, const long long *d_frame_off,
                          const int *d_frame_hw, const double *d_dets, int det_stride,
                          const int *d_det_off, double *d_warps);
+/* Tensor apply: the frames and the detection rows are read where they are in device memory, and
+ * the call is stream-ordered with no host wait (the protocol of yta_bytetrack_update_tensors: the
+ * host arrays go into a ring of mapped page-locked slots, an event hands over from caller_stream
+ * to the engine's stream, the frame runs there as plain launches, a second event hands back; a
+ * slot is reused after its event has completed; a capturing caller_stream is refused).  To the
+ * caller it behaves like one kernel on caller_stream: the inputs may be overwritten right after
+ * it, d_warps is visible to later work on that stream.
+ *   frames: S device addresses, stream s's first pixel; frame_hw[2 s] = h, frame_hw[2 s + 1] = w;
+ *     frame_pitch[s]: bytes between rows (>= 3 w, below 2^31, no alignment requirement; pixel
+ *     stride 3).
+ *     frames, frame_hw, frame_pitch and det_counts are host arrays, copied during the call.
+ *   d_dets: rows of dtype (YTA_F64 / YTA_F32 / YTA_F16), row_stride elements apart (>= 4; >= 5
+ *     with conf_thresh), x1 y1 x2 y2 [conf] first, stream s's det_counts[s] rows after stream
+ *     s - 1's; promoted to float64 (exact).  conf_thresh (nullable): only rows with
+ *     (double)row[4] > *conf_thresh enter the first frame's mask (the rows the trackers pass,
+ *     bot_sort.py:266-267, deep_ocsort.py:378-379); a NaN confidence is excluded.
+ *   d_warps: S x 6 float64 out, device memory.
+ * A frame larger than max_h x max_w grows the engine as yta_sof_apply does (a host wait, counted);
+ * the synchronous entry points wait for the engine's stream and so see the frames in flight. */
+int yta_sof_apply_tensors(yta_sof *engine, void *caller_stream, const void *const *frames,
+                          const int *frame_hw, const long long *frame_pitch, const void *d_dets,
+                          int dtype, long long row_stride, const int *det_counts,
+                          const double *conf_thresh, double *d_warps);
+/* Accounting of the tensor path (writes min(n, 2) int64): frames enqueued; host_waits, the calls
+ * that blocked on the device (engine growth, or 64 frames in flight). */
+int yta_sof_tensor_stats(yta_sof *engine, long long *out, int n);
 int yta_sof_sync(yta_sof *engine);
 /* Parity introspection of stream s: the stored corners (prev_keypoints, n x 2 float32, up to
  * cap), whether the stream has its first frame, and the stored previous gray frame (h x w uint8,
@@ -796,6 +834,15 @@ int yta_ecc_apply(yta_ecc *engine, const uint8_t *frames, const long long *frame
 /* Device-buffer apply (asynchronous on the engine stream), then yta_ecc_sync. */
 int yta_ecc_apply_device(yta_ecc *engine, const uint8_t *d_frames, const long long *d_frame_off,
                          const int *d_frame_hw, float *d_warps);
+/* Tensor apply: as yta_sof_apply_tensors without detections; d_warps: S x 6 float32 out, device
+ * memory.  The engine keeps its own copy of every estimate, so yta_ecc_aligned does not read
+ * d_warps again (it may be recycled by then).  A larger frame grows the slots (a host wait,
+ * counted); one whose warp tables would not fit the LDS stage is refused with YTA_ERR_CAPACITY
+ * before anything is enqueued, and the engine is left as it was. */
+int yta_ecc_apply_tensors(yta_ecc *engine, void *caller_stream, const void *const *frames,
+                          const int *frame_hw, const long long *frame_pitch, float *d_warps);
+/* As yta_sof_tensor_stats. */
+int yta_ecc_tensor_stats(yta_ecc *engine, long long *out, int n);
 int yta_ecc_sync(yta_ecc *engine);
 /* Last apply per stream (each array S entries, may be NULL): outcome 0 first frame, 1 estimated,
  * 2 identity (OpenCV would have raised); Gauss-Newton iterations run; the final correlation rho. */

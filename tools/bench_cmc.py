@@ -7,7 +7,10 @@ stored corners, RANSAC + LM).  Frames: a textured scene per stream seen through 
 window (integer shifts of a few px per frame).  CPU leg: oracle/cmc_sof.py (NumPy restatement) on
 one stream, 1 thread, a bounded sample of the same frames.  Prints one JSON line.
 --estimator ecc: the ECC estimator instead (ecc.py, csrc/ecc.hip: one yta_ecc_apply_device call
-per step, warp_mode --warp-mode, default euclidean), its CPU leg oracle/cmc_ecc.py."""
+per step, warp_mode --warp-mode, default euclidean), its CPU leg oracle/cmc_ecc.py.
+--tensors: instead, what a caller sees per call (wall clock, each timed run ending in a device
+wait, best of three fresh engines): the host-buffer apply() on NumPy frames, which uploads them,
+against apply_tensors() on the same frames staged in HBM as separate tensors."""
 import argparse
 import ctypes
 import json
@@ -35,6 +38,53 @@ def frames_for(S, F, H, W, seed):
     return out
 
 
+def tensors_leg(args, fr, dets):
+    """Wall ms per call of apply() (host frames) and apply_tensors() (frames in HBM)."""
+    import torch
+    from yolo_tracking_amd.motion.ecc import EccEngine
+    from yolo_tracking_amd.motion.sof import SofEngine
+    F, S, H, W = fr.shape[:4]
+    ecc = args.estimator == "ecc"
+    d_fr = [[torch.from_numpy(fr[f, s]).cuda() for s in range(S)] for f in range(F)]
+    per = [dets[s * args.dets:(s + 1) * args.dets] for s in range(S)]
+    d_dets = torch.from_numpy(dets).cuda()
+    counts = [args.dets] * S
+
+    def make():
+        return EccEngine(S, args.warp_mode, 1e-5, 100, args.scale, 0, H, W) if ecc \
+            else SofEngine(S, args.scale, 0, H, W)
+
+    def host(eng, f):
+        return eng.apply(list(fr[f])) if ecc else eng.apply(list(fr[f]), per)
+
+    def tens(eng, f):
+        return eng.apply_tensors(d_fr[f]) if ecc else eng.apply_tensors(d_fr[f], d_dets, counts)
+
+    out = {}
+    for name, call in (("host_ms_per_call", host), ("tensors_ms_per_call", tens)):
+        best = None
+        for _ in range(3):
+            eng = make()
+            call(eng, 0)
+            call(eng, 1)          # pre-roll: first frame and one steady-state frame
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for f in range(2, F):
+                call(eng, f)
+            eng.outcome()         # waits for the engine's stream
+            torch.cuda.synchronize()
+            ms = 1000 * (time.perf_counter() - t0) / (F - 2)
+            best = ms if best is None else min(best, ms)
+            eng.close()
+        out[name] = best
+    name = "ECC" if ecc else "SparseOptFlow"
+    print(json.dumps({"metric": f"{name} apply() vs apply_tensors() ms/call", "streams": S,
+                      "frame": f"{W}x{H}", "scale": args.scale, "steps": F - 2,
+                      "dets_per_stream": args.dets, **out,
+                      "frame_bytes_uploaded_per_call_host": int(S * H * W * 3),
+                      "frame_bytes_uploaded_per_call_tensors": 0}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=64)
@@ -47,6 +97,8 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--estimator", choices=["sof", "ecc"], default="sof")
     ap.add_argument("--warp-mode", type=int, default=1, help="ECC: 0 translation, 1 euclidean, 2 affine")
+    ap.add_argument("--tensors", action="store_true",
+                    help="host-buffer apply() against apply_tensors() on frames staged in HBM")
     args = ap.parse_args()
     import torch
     from yolo_tracking_amd import _lib
@@ -59,6 +111,8 @@ def main():
     wh = rng.uniform(40, 200, (S, args.dets, 2))
     dets = np.concatenate([xy, xy + wh], 2).reshape(-1, 4)
     gen_s = time.time() - t0
+    if args.tensors:
+        return tensors_leg(args, fr, dets)
     d = torch.device("cuda", 0)
     d_fr = torch.from_numpy(fr.reshape(F, -1)).to(d)
     d_off = torch.arange(S, dtype=torch.int64, device=d) * (H * W * 3)

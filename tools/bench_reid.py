@@ -3,7 +3,9 @@ one 1920x1080 BGR image per stream, boxes from the §8(d) generator scaled to th
 of every stream in one yta_reid_preprocess_device launch, images and boxes resident in HBM.
 Roofline: HBM writes of the float32 / float16 NCHW crops (+ the crop source bytes, read once).
 CPU leg: oracle/reid.py (the NumPy restatement of the reference's per-crop loop) on a bounded
-sample.  Prints one JSON line."""
+sample.  Prints one JSON line.
+--tensors: the same crops through yta_reid_preprocess_tensors, every stream's image a separate
+device tensor and the boxes float32 rows of a (n, 6) tensor read in place."""
 import argparse
 import ctypes
 import json
@@ -24,6 +26,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--half", type=int, default=0)
     ap.add_argument("--cpu-sample", type=int, default=256)
+    ap.add_argument("--tensors", action="store_true",
+                    help="the tensor-image form (pointer table, float32 strided boxes)")
     args = ap.parse_args()
     import torch
     from yolo_tracking_amd import _lib
@@ -45,7 +49,21 @@ def main():
     out = torch.empty((n, 3, 256, 128), dtype=torch.half if args.half else torch.float, device=d)
     st = torch.cuda.current_stream(d)
 
+    if args.tensors:
+        t_img = [torch.from_numpy(imgs[s]).to(d) for s in range(S)]
+        t_ptr = torch.tensor([t.data_ptr() for t in t_img], dtype=torch.int64, device=d)
+        t_pitch = torch.full((S,), 3 * W, dtype=torch.int64, device=d)
+        t_box = torch.zeros((n, 6), dtype=torch.float32, device=d)
+        t_box[:, :4] = torch.from_numpy(boxes).to(d)
+
     def launch():
+        if args.tensors:
+            _lib.check(lib.yta_reid_preprocess_tensors(
+                ctypes.c_void_p(t_ptr.data_ptr()), ctypes.c_void_p(d_hw.data_ptr()),
+                ctypes.c_void_p(t_pitch.data_ptr()), ctypes.c_void_p(t_box.data_ptr()),
+                _lib.YTA_F32, 6, ctypes.c_void_p(d_own.data_ptr()), n, 256, 128, args.half,
+                ctypes.c_void_p(out.data_ptr()), None, ctypes.c_void_p(st.cuda_stream)))
+            return
         _lib.check(lib.yta_reid_preprocess_device(
             ctypes.c_void_p(d_img.data_ptr()), ctypes.c_void_p(d_off.data_ptr()),
             ctypes.c_void_p(d_hw.data_ptr()), ctypes.c_void_p(d_box.data_ptr()),
@@ -84,6 +102,7 @@ def main():
     print(json.dumps({"metric": "ReID crops preprocessed/s", "value": n / (ms * 1e-3),
                       "unit": "crops/s", "ms_per_launch": ms, "crops_per_launch": n,
                       "dtype": "f16" if args.half else "f32",
+                      "form": "tensors" if args.tensors else "device",
                       "config": {"workload": f"{S} streams x {M} dets, 1920x1080 BGR, 128x256 crops"},
                       "roofline": {"bound": "hbm", "achieved": gbs, "peak": 8000.0, "unit": "GB/s",
                                    "frac": gbs / 8000.0,

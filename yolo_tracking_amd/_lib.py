@@ -214,6 +214,7 @@ _SIGS = {
     "yta_aw_max_metric": ([_I, _P, _I, _I, ctypes.c_double, ctypes.c_double, _P], _I),
     "yta_reid_preprocess": ([_I, _P, _I, _I, _P, _I, _I, _I, _I, _P], _I),
     "yta_reid_preprocess_device": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P], _I),
+    "yta_reid_preprocess_tensors": ([_P, _P, _P, _P, _I, _LL, _P, _I, _I, _I, _I, _P, _P, _P], _I),
     "yta_reid_normalize": ([_I, _P, ctypes.c_longlong], _I),
     "yta_reid_normalize_device": ([_P, ctypes.c_longlong, _P, _P], _I),
     "yta_sof_create": ([_I, _I, _D, _I, _I, _P], _I),
@@ -221,6 +222,8 @@ _SIGS = {
     "yta_sof_reset": ([_P], _I),
     "yta_sof_apply": ([_P, _P, _P, _P, _P, _I, _P, _P], _I),
     "yta_sof_apply_device": ([_P, _P, _P, _P, _P, _I, _P, _P], _I),
+    "yta_sof_apply_tensors": ([_P, _P, _P, _P, _P, _P, _I, _LL, _P, _P, _P], _I),
+    "yta_sof_tensor_stats": ([_P, _P, _I], _I),
     "yta_sof_sync": ([_P], _I),
     "yta_sof_get_state": ([_P, _I, _P, _P, _P, _I, _P, _P, _P, _I], _I),
     "yta_sof_outcome": ([_P, _P], _I),
@@ -235,6 +238,8 @@ _SIGS = {
     "yta_ecc_reset": ([_P], _I),
     "yta_ecc_apply": ([_P, _P, _P, _P, _P], _I),
     "yta_ecc_apply_device": ([_P, _P, _P, _P, _P], _I),
+    "yta_ecc_apply_tensors": ([_P, _P, _P, _P, _P, _P], _I),
+    "yta_ecc_tensor_stats": ([_P, _P, _I], _I),
     "yta_ecc_sync": ([_P], _I),
     "yta_ecc_outcome": ([_P, _P, _P, _P], _I),
     "yta_ecc_get_state": ([_P, _I, _P, _P, _P, _P, _I], _I),

@@ -6,6 +6,10 @@ runs the ReID network (`forward`, :226-299) and divides the features by one glob
 (`get_features`, :303-311).  Here the image goes to HBM once and `yta_reid_preprocess_device`
 writes every crop of every camera stream in one launch, straight into the NCHW tensor the network
 reads; `yta_reid_normalize_device` does the global normalisation before the single copy back.
+An image that is already a CUDA tensor (uint8 (h, w, 3), rows any pitch >= 3 * w) is read where it
+is (`yta_reid_preprocess_tensors`), with NumPy or CUDA boxes; CUDA boxes (float64 / float32 /
+float16 rows, a column slice of a wider tensor included) never reach the host, so an empty crop is
+then a zero crop instead of an error.
 
 The network: OSNet (appearance/osnet.py, an eval-mode inference graph with folded BatchNorms,
 channels-last, batched branches) built from `weights` as the reference builds it from the weight
@@ -121,9 +125,64 @@ class ReIDDetectMultiBackend:
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _preprocess_tensors(self, items):
+        """preprocess_batch when an image or a box array is a CUDA tensor: the frames through a
+        pointer table, the boxes where they are.  Sizes come from the tensors' shapes; the small
+        tables go up from page-locked memory on the current stream, so nothing waits."""
+        from ..trackers._tensors import _dtype_codes, _pack, frame_table, is_cuda_tensor
+        torch, d = self.torch, self.device
+        codes = _dtype_codes(torch)
+        imgs, boxes, owner = [], [], []
+        for i, (xyxys, img) in enumerate(items):
+            if not is_cuda_tensor(img):
+                img = torch.from_numpy(np.ascontiguousarray(img, dtype=np.uint8)).to(d)
+            imgs.append(img)
+            if is_cuda_tensor(xyxys):
+                if xyxys.dim() != 2 or xyxys.shape[1] < 4 or xyxys.dtype not in codes or \
+                        xyxys.device != img.device:
+                    raise ValueError(f"boxes of image {i}: expected a float64 / float32 / float16 "
+                                     f"(n, >= 4) tensor on {img.device}, got {xyxys.dtype} "
+                                     f"{tuple(xyxys.shape)} on {xyxys.device}")
+                b = xyxys[:, :4]
+            else:
+                b = np.asarray(xyxys, dtype=np.float64).reshape(-1, 4)
+                _check_crops(b, int(img.shape[0]), int(img.shape[1]))
+                b = torch.from_numpy(np.ascontiguousarray(b)).to(d)
+            boxes.append(b)
+            owner.append(np.full(b.shape[0], i, dtype=np.int32))
+        imgs, ptr, hw, pitch = frame_table(imgs, len(imgs), d.index, "img")
+        n = int(sum(b.shape[0] for b in boxes))
+        out = torch.empty((n, 3, OUT_H, OUT_W), dtype=torch.half if self.fp16 else torch.float,
+                          device=d)
+        if n == 0:
+            return out
+        if len({b.dtype for b in boxes}) != 1:   # promotion to float64 is exact
+            boxes = [b.double() for b in boxes]
+        rows, row_stride = _pack(torch, boxes, 4)
+        # one table: addresses, pitches, (h, w) pairs, then the owner of every box
+        k = len(imgs)
+        meta = np.zeros(3 * k + (n + 1) // 2, dtype=np.int64)
+        meta[:k] = ptr.view(np.int64)
+        meta[k:2 * k] = pitch
+        meta[2 * k:3 * k] = hw.view(np.int64)
+        meta[3 * k:].view(np.int32)[:n] = np.concatenate(owner)
+        d_meta = torch.from_numpy(meta).pin_memory().to(d, non_blocking=True)
+        p0 = d_meta.data_ptr()
+        _lib.check(self.lib.yta_reid_preprocess_tensors(
+            ctypes.c_void_p(p0), ctypes.c_void_p(p0 + 16 * k), ctypes.c_void_p(p0 + 8 * k),
+            ctypes.c_void_p(rows.data_ptr()), codes[rows.dtype], int(row_stride),
+            ctypes.c_void_p(p0 + 24 * k), n, OUT_H, OUT_W, int(self.fp16),
+            ctypes.c_void_p(out.data_ptr()), None, self._stream()))
+        return out
+
     def preprocess_batch(self, items):
         """One launch for the boxes of several images: items = [(xyxys, img), ...] -> (sum n, 3,
-        256, 128) device tensor, crops in item order."""
+        256, 128) device tensor, crops in item order.  An image may be a CUDA uint8 (h, w, 3)
+        tensor and the boxes a CUDA tensor (see _preprocess_tensors); with NumPy boxes an empty
+        crop raises as in the reference, with CUDA boxes it is a zero crop."""
+        from ..trackers._tensors import is_cuda_tensor
+        if any(is_cuda_tensor(img) or is_cuda_tensor(b) for b, img in items):
+            return self._preprocess_tensors(items)
         torch = self.torch
         boxes, owner, offs, hws, bufs = [], [], [], [], []
         off = 0
@@ -199,9 +258,11 @@ class ReIDDetectMultiBackend:
     def get_features(self, xyxys, img, as_tensor=False):
         """:303-311: features of the crops, divided by their global norm (NumPy (N, D)).
         as_tensor: hand the same normalised features back as a device tensor instead (the
-        trackers' tensor path, where the embeddings never leave HBM)."""
+        trackers' tensor path, where the embeddings never leave HBM).  img and xyxys may be CUDA
+        tensors (preprocess_batch)."""
         torch = self.torch
-        if np.asarray(xyxys).size == 0:
+        on_device = type(xyxys).__module__.split(".")[0] == "torch" and xyxys.is_cuda
+        if (xyxys.shape[0] if on_device else np.asarray(xyxys).size) == 0:
             return torch.empty((0, 0), device=self.device) if as_tensor else np.array([])
         with torch.no_grad():
             crops = self.preprocess(xyxys, img)

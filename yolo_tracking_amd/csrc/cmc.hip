@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "cmc_small.hpp"
+#include "cmc_tensors.hpp"
 #include "common.hpp"
 
 namespace yta {
@@ -80,12 +81,19 @@ struct SofArgs {
     unsigned long long *keys;   // [S][keys_cap]
     long long keys_cap;
     SofState *state;
-    // per frame
+    // per frame.  Frame s starts at frame_ptr[s] with rows frame_pitch[s] bytes apart (the tensor
+    // form's pointer table), or, with a null table, at frames + frame_off[s] with rows of 3 * w
+    // bytes (one packed allocation).
     const uint8_t *frames;
     const long long *frame_off;
+    const uint8_t *const *frame_ptr;
+    const long long *frame_pitch;
     const int *frame_hw;
-    const double *dets;
-    int det_stride;
+    const void *dets;    // rows of det_dtype (YTA_F64 / YTA_F32 / YTA_F16), det_stride elements apart
+    int det_dtype;
+    long long det_stride;
+    int det_select;      // 1: only rows with (double)row[4] > det_thresh enter the mask
+    double det_thresh;
     const int *det_off;
     double *warps;       // [S][6]
 };
@@ -171,7 +179,9 @@ __global__ __launch_bounds__(256) void k_sof_small(SofArgs a) {
     if (i >= h0 * w0) return;
     const int oy = i / w0, ox = i - oy * w0;
     uint8_t *dst = a.img + ((long long)s * 2 + cur) * a.slot_px;
-    dst[i] = (uint8_t)small_pixel(a.frames + a.frame_off[s], H, W, a.scale, ox, oy);
+    global_u8 *f = (global_u8 *)(a.frame_ptr ? a.frame_ptr[s] : a.frames + a.frame_off[s]);
+    const int pitch = a.frame_pitch ? (int)a.frame_pitch[s] : 3 * W;
+    dst[i] = (uint8_t)small_pixel(f, H, W, pitch, a.scale, ox, oy);
 }
 
 // --------------------------------------------------------------------------------- k_sof_pyr
@@ -407,10 +417,12 @@ __global__ __launch_bounds__(GFTT_T) void k_sof_gftt(SofArgs a) {
     block_sync();
     const int d0 = a.det_off[s], nd = a.det_off[s + 1] - d0;
     for (int k = t; k < nd; k += nt) {
-        const double *d = a.dets + (long long)(d0 + k) * a.det_stride;
+        // the row where the caller keeps it, promoted exactly; a NaN confidence fails the test
+        const long long d = (long long)(d0 + k) * a.det_stride;
+        if (a.det_select && !(det_el(a.dets, a.det_dtype, d + 4) > a.det_thresh)) continue;
         long long tl[4];
         for (int q = 0; q < 4; ++q) {
-            const double v = d[q] * a.scale;
+            const double v = det_el(a.dets, a.det_dtype, d + q) * a.scale;
             tl[q] = isfinite(v) ? (long long)v : 0;   // astype(int) truncates
         }
         const int2 ry = py_slice(tl[1], tl[3], h), rx = py_slice(tl[0], tl[2], w);
@@ -1089,7 +1101,7 @@ __global__ __launch_bounds__(256) void k_kat_small(const uint8_t *f, int H, int 
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= h0 * w0) return;
     const int oy = i / w0, ox = i - oy * w0;
-    out[i] = (uint8_t)small_pixel(f, H, W, scale, ox, oy);
+    out[i] = (uint8_t)small_pixel(f, H, W, 3 * W, scale, ox, oy);
 }
 
 __global__ __launch_bounds__(GFTT_T) void k_kat_eig(const uint8_t *g, int h, int w, float *cov,
@@ -1157,6 +1169,7 @@ struct yta_sof {
     int *d_det_off = nullptr;
     double *d_warps = nullptr;
     SofState *h_state = nullptr;
+    CmcTensors t;   // the tensor path (yta_sof_apply_tensors)
 };
 
 namespace {
@@ -1276,6 +1289,42 @@ int check_frames(yta_sof *e, const long long *frame_off, const int *frame_hw, lo
     return YTA_OK;
 }
 
+// Frames up to mh x mw: grow, keeping every stream's state (a host wait; nothing happens when
+// they fit already).
+int sof_grow(yta_sof *e, int mh, int mw) {
+    if (mh <= e->max_h && mw <= e->max_w) return YTA_OK;
+    const int S = e->S;
+    int rc;
+    // grow, keeping every stream's state: the stored frame's pyramid and derivatives (packed
+    // from the slot start at the stored frame's own size), the corners and SofState
+    YTA_HIP(host_wait(e->stream));
+    const SofArgs old = e->a;
+    std::vector<void *> old_allocs;
+    old_allocs.swap(e->allocs);
+    if (e->h_state) (void)hipHostFree(e->h_state);
+    e->h_state = nullptr;
+    e->max_h = mh;
+    e->max_w = mw;
+    rc = sof_buffers(e);
+    if (!rc) rc = yta_sof_reset(e);
+    if (!rc) {
+        SofArgs &a = e->a;
+        const size_t rows = (size_t)S * 2;
+        YTA_HIP(hipMemcpy2DAsync(a.img, a.slot_px, old.img, old.slot_px, old.slot_px, rows,
+                                 hipMemcpyDeviceToDevice, e->stream));
+        YTA_HIP(hipMemcpy2DAsync(a.der, a.slot_px * sizeof(short2), old.der,
+                                 old.slot_px * sizeof(short2), old.slot_px * sizeof(short2),
+                                 rows, hipMemcpyDeviceToDevice, e->stream));
+        YTA_HIP(hipMemcpyAsync(a.kp, old.kp, sizeof(float2) * S * SOF_MAXKP,
+                               hipMemcpyDeviceToDevice, e->stream));
+        YTA_HIP(hipMemcpyAsync(a.state, old.state, sizeof(SofState) * S,
+                               hipMemcpyDeviceToDevice, e->stream));
+        rc = host_wait(e->stream) == hipSuccess ? YTA_OK : YTA_ERR_HIP;
+    }
+    for (void *p : old_allocs) (void)hipFree(p);
+    return rc;
+}
+
 }  // namespace
 
 namespace {
@@ -1358,6 +1407,7 @@ int yta_sof_destroy(yta_sof *e) {
     (void)hipSetDevice(e->device);
     if (e->stream) (void)host_wait(e->stream);
     sof_free(e);
+    cmc_tensors_free(e->t);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
     return YTA_OK;
@@ -1381,9 +1431,14 @@ int yta_sof_apply_device(yta_sof *e, const uint8_t *d_frames, const long long *d
     SofArgs &a = e->a;
     a.frames = d_frames;
     a.frame_off = d_frame_off;
+    a.frame_ptr = nullptr;
+    a.frame_pitch = nullptr;
     a.frame_hw = d_frame_hw;
     a.dets = d_dets;
+    a.det_dtype = YTA_F64;
     a.det_stride = det_stride;
+    a.det_select = 0;
+    a.det_thresh = 0.0;
     a.det_off = d_det_off;
     a.warps = d_warps;
     return sof_launch(e);
@@ -1419,36 +1474,8 @@ int yta_sof_apply(yta_sof *e, const uint8_t *frames, const long long *frame_off,
         mw = std::max(mw, frame_hw[2 * s + 1]);
         YTA_CHECK(det_off[s + 1] >= det_off[s], YTA_ERR_INVALID, "det_off must be non-decreasing");
     }
-    if (mh > e->max_h || mw > e->max_w) {
-        // grow, keeping every stream's state: the stored frame's pyramid and derivatives (packed
-        // from the slot start at the stored frame's own size), the corners and SofState
-        YTA_HIP(host_wait(e->stream));
-        const SofArgs old = e->a;
-        std::vector<void *> old_allocs;
-        old_allocs.swap(e->allocs);
-        if (e->h_state) (void)hipHostFree(e->h_state);
-        e->h_state = nullptr;
-        e->max_h = mh;
-        e->max_w = mw;
-        rc = sof_buffers(e);
-        if (!rc) rc = yta_sof_reset(e);
-        if (!rc) {
-            SofArgs &a = e->a;
-            const size_t rows = (size_t)S * 2;
-            YTA_HIP(hipMemcpy2DAsync(a.img, a.slot_px, old.img, old.slot_px, old.slot_px, rows,
-                                     hipMemcpyDeviceToDevice, e->stream));
-            YTA_HIP(hipMemcpy2DAsync(a.der, a.slot_px * sizeof(short2), old.der,
-                                     old.slot_px * sizeof(short2), old.slot_px * sizeof(short2),
-                                     rows, hipMemcpyDeviceToDevice, e->stream));
-            YTA_HIP(hipMemcpyAsync(a.kp, old.kp, sizeof(float2) * S * SOF_MAXKP,
-                                   hipMemcpyDeviceToDevice, e->stream));
-            YTA_HIP(hipMemcpyAsync(a.state, old.state, sizeof(SofState) * S,
-                                   hipMemcpyDeviceToDevice, e->stream));
-            rc = host_wait(e->stream) == hipSuccess ? YTA_OK : YTA_ERR_HIP;
-        }
-        for (void *p : old_allocs) (void)hipFree(p);
-        if (rc) return rc;
-    }
+    rc = sof_grow(e, mh, mw);
+    if (rc) return rc;
     if (bytes > e->frames_cap) {
         if (e->d_frames) (void)hipFree(e->d_frames);
         e->d_frames = nullptr;
@@ -1481,6 +1508,66 @@ int yta_sof_apply(yta_sof *e, const uint8_t *frames, const long long *frame_off,
     YTA_HIP(hipMemcpyAsync(warps, e->d_warps, sizeof(double) * 6 * S, hipMemcpyDeviceToHost,
                            e->stream));
     return yta_sof_sync(e);
+}
+
+int yta_sof_apply_tensors(yta_sof *e, void *caller_stream, const void *const *frames,
+                          const int *frame_hw, const long long *frame_pitch, const void *d_dets,
+                          int dtype, long long row_stride, const int *det_counts,
+                          const double *conf_thresh, double *d_warps) {
+    YTA_CHECK(e && det_counts && d_warps, YTA_ERR_INVALID, "null argument");
+    YTA_CHECK(dtype == YTA_F64 || dtype == YTA_F32 || dtype == YTA_F16, YTA_ERR_INVALID,
+              "dtype %d is none of YTA_F64, YTA_F32, YTA_F16", dtype);
+    YTA_CHECK(row_stride >= (conf_thresh ? 5 : 4), YTA_ERR_INVALID,
+              "row_stride %lld < %d (x1 y1 x2 y2%s)", row_stride, conf_thresh ? 5 : 4,
+              conf_thresh ? " conf, which conf_thresh reads" : "");
+    const int S = e->S;
+    long long total = 0;
+    for (int s = 0; s < S; ++s) {
+        YTA_CHECK(det_counts[s] >= 0, YTA_ERR_INVALID, "det_counts[%d] is negative", s);
+        total += det_counts[s];
+    }
+    YTA_CHECK(total <= 0x7fffffffLL, YTA_ERR_INVALID, "%lld detections in one frame", total);
+    const size_t esz = dtype == YTA_F64 ? 8 : dtype == YTA_F32 ? 4 : 2;
+    YTA_CHECK(total == 0 || (d_dets && (uintptr_t)d_dets % esz == 0), YTA_ERR_INVALID,
+              "d_dets null or not aligned to its element size");
+    YTA_HIP(hipSetDevice(e->device));
+    const hipStream_t cs = (hipStream_t)caller_stream;
+    int rc = cmc_check_frames(S, cs, frames, frame_hw, frame_pitch);
+    if (rc) return rc;
+    int mh = e->max_h, mw = e->max_w;
+    for (int s = 0; s < S; ++s) {
+        mh = std::max(mh, frame_hw[2 * s]);
+        mw = std::max(mw, frame_hw[2 * s + 1]);
+    }
+    if (mh > e->max_h || mw > e->max_w) {   // sizes are known here: grow as yta_sof_apply does
+        ++e->t.stat[CTS_HOST_WAITS];
+        rc = sof_grow(e, mh, mw);
+        if (rc) return rc;
+    }
+    CmcSlot *slot = nullptr;
+    rc = cmc_hand_in(e->t, S, cs, e->stream, frames, frame_hw, frame_pitch, det_counts, &slot);
+    if (rc) return rc;
+    SofArgs &a = e->a;
+    a.frames = nullptr;
+    a.frame_off = nullptr;
+    a.frame_ptr = e->t.ptr;
+    a.frame_pitch = e->t.pitch;
+    a.frame_hw = e->t.hw;
+    a.dets = d_dets;
+    a.det_dtype = dtype;
+    a.det_stride = row_stride;
+    a.det_select = conf_thresh ? 1 : 0;
+    a.det_thresh = conf_thresh ? *conf_thresh : 0.0;
+    a.det_off = e->t.off;
+    a.warps = d_warps;
+    rc = sof_launch(e);
+    if (rc) return rc;
+    return cmc_hand_back(slot, cs, e->stream);
+}
+
+int yta_sof_tensor_stats(yta_sof *e, long long *out, int n) {
+    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
+    return cmc_tensor_stats(e->t, out, n);
 }
 
 int yta_sof_get_state(yta_sof *e, int stream, int *initialized, int *n_kp, float *kp, int cap,

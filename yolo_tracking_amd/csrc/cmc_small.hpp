@@ -12,6 +12,11 @@
 namespace yta {
 namespace cmc {
 
+// A frame address read from a pointer table is a generic pointer to the compiler, which then emits
+// flat loads; frames are in global memory, and a pointer type that says so keeps the loads
+// global_load_*, as they are for a kernel-argument pointer.
+typedef __attribute__((address_space(1))) const uint8_t global_u8;
+
 // borderInterpolate(p, n, BORDER_REFLECT_101)
 __device__ __forceinline__ int refl(int p, int n) {
     if ((unsigned)p < (unsigned)n) return p;
@@ -24,14 +29,19 @@ __device__ __forceinline__ int refl(int p, int n) {
 
 // cvtColor(BGR2GRAY) (8u fixed point) + cv2.resize(img, (0, 0), fx=scale, fy=scale,
 // INTER_LINEAR) (oracle/reid.py resize_linear_u8 with fx / fy) for one output pixel.
-__device__ __forceinline__ int bgr_gray(const uint8_t *p) {
+template <typename P>
+__device__ __forceinline__ int bgr_gray(P p) {
     return ((int)p[0] * 1868 + (int)p[1] * 9617 + (int)p[2] * 4899 + (1 << 13)) >> 14;
 }
 
-__device__ __forceinline__ int small_pixel(const uint8_t *f, int H, int W, double inv, int ox,
+// f: the frame's first pixel; rows are `pitch` bytes apart (>= 3 * W, any alignment: every pixel
+// is three byte loads; below 2^31, so a row's offset is one 32 x 32 -> 64 bit multiply-add), pixels
+// 3 bytes apart.
+template <typename P>
+__device__ __forceinline__ int small_pixel(P f, int H, int W, int pitch, double inv, int ox,
                                            int oy) {
     const double sc = 1.0 / inv;
-    auto g = [&](int y, int x) { return bgr_gray(f + ((long long)y * W + x) * 3); };
+    auto g = [&](int y, int x) { return bgr_gray(f + (long long)y * pitch + x * 3); };
     if (fabs(sc - 2.0) < DBL_EPSILON) {   // INTER_AREA fast path (exact 2x)
         const int x0 = min(2 * ox, W - 1), x1 = min(2 * ox + 1, W - 1);
         const int y0 = min(2 * oy, H - 1), y1 = min(2 * oy + 1, H - 1);

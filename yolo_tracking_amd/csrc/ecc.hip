@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "cmc_small.hpp"
+#include "cmc_tensors.hpp"
 #include "common.hpp"
 
 namespace yta {
@@ -63,10 +64,15 @@ struct EccArgs {
     double eps;
     uint8_t *img;        // [S][2][slot_px]
     EccState *state;
+    // frame s: frame_ptr[s] with rows frame_pitch[s] bytes apart (the tensor form's pointer
+    // table), or, with a null table, frames + frame_off[s] with rows of 3 * w bytes
     const uint8_t *frames;
     const long long *frame_off;
+    const uint8_t *const *frame_ptr;
+    const long long *frame_pitch;
     const int *frame_hw;
-    float *warps;        // [S][6]
+    float *warps;        // [S][6] the caller's output
+    float *kept;         // [S][6] engine-owned copy of the last estimate (k_ecc_align reads it)
 };
 
 __host__ __device__ constexpr int ecc_nparams(int mode) {
@@ -115,7 +121,9 @@ __global__ __launch_bounds__(256) void k_ecc_small(EccArgs a) {
     if (i >= h0 * w0) return;
     const int oy = i / w0, ox = i - oy * w0;
     uint8_t *dst = a.img + ((long long)s * 2 + cur) * a.slot_px;
-    dst[i] = (uint8_t)small_pixel(a.frames + a.frame_off[s], H, W, a.scale, ox, oy);
+    global_u8 *f = (global_u8 *)(a.frame_ptr ? a.frame_ptr[s] : a.frames + a.frame_off[s]);
+    const int pitch = a.frame_pitch ? (int)a.frame_pitch[s] : 3 * W;
+    dst[i] = (uint8_t)small_pixel(f, H, W, pitch, a.scale, ox, oy);
 }
 
 // ------------------------------------------------------------------------------------ k_ecc
@@ -679,7 +687,10 @@ __global__ __launch_bounds__(ecc_threads(MODE)) void k_ecc(EccArgs a) {
         sv.m[5] = sv.m[5] / (float)a.scale;
     }
     __syncthreads();
-    if (t < 6) W[t] = sv.m[t];
+    if (t < 6) {
+        W[t] = sv.m[t];
+        a.kept[6 * (long long)s + t] = sv.m[t];   // the caller's buffer may be recycled
+    }
     if (t == 0) {
         st.prev = cur;   // ecc.py:102
         st.outcome = ECC_OUT_EST;
@@ -707,7 +718,7 @@ __global__ __launch_bounds__(256) void k_ecc_align(EccArgs a, int s, uint8_t *ou
     const int y = i / w, x = i - y * w;
     double M[6];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) M[k] = (double)a.warps[6 * s + k];
+    for (int k = 0; k < 6; ++k) M[k] = (double)a.kept[6 * s + k];
     double D = M[0] * M[4] - M[1] * M[3];
     D = D != 0.0 ? 1.0 / D : 0.0;
     const double A11 = M[4] * D, A22 = M[0] * D;
@@ -751,6 +762,8 @@ struct yta_ecc {
     uint8_t *img = nullptr;
     EccState *state = nullptr;
     float *d_warps = nullptr;
+    float *d_kept = nullptr;        // the last estimate of every stream (EccArgs::kept)
+    CmcTensors t;                   // the tensor path (yta_ecc_apply_tensors)
     uint8_t *d_frames = nullptr;
     long long frames_cap = 0;
     long long *d_frame_off = nullptr;
@@ -811,6 +824,7 @@ int set_ecc_lds() {
 int ecc_launch(yta_ecc *e) {
     EccArgs &a = e->a;
     a.state = e->state;
+    a.kept = e->d_kept;
     a.mode = e->mode;
     a.max_iter = e->max_iter;
     a.eps = e->eps;
@@ -827,6 +841,26 @@ int ecc_launch(yta_ecc *e) {
     YTA_HIP(hipLaunchKernel(packed ? ecc_kernel<true>(e->mode) : ecc_kernel<false>(e->mode),
                             dim3(a.S), dim3(ecc_threads(e->mode)), args, lds, e->stream));
     return YTA_OK;
+}
+
+// Frames up to mh x mw: grow the slots, keeping every stream's previous frame (packed from the
+// slot start).  A host wait; nothing happens when they fit already.  On failure the engine keeps
+// its previous slots and size untouched.
+int ecc_grow(yta_ecc *e, int mh, int mw) {
+    if (mh <= e->max_h && mw <= e->max_w) return YTA_OK;
+    YTA_HIP(host_wait(e->stream));
+    uint8_t *old = nullptr;
+    long long old_px = 0;
+    int rc = ecc_slots(e, mh, mw, &old, &old_px);
+    if (rc) return rc;
+    if (old) {
+        if (hipMemcpy2DAsync(e->img, e->a.slot_px, old, old_px, old_px, (size_t)e->S * 2,
+                             hipMemcpyDeviceToDevice, e->stream) != hipSuccess ||
+            host_wait(e->stream) != hipSuccess)
+            rc = YTA_ERR_HIP;
+        (void)hipFree(old);
+    }
+    return rc;
 }
 
 }  // namespace
@@ -871,6 +905,7 @@ int yta_ecc_create(int device, int n_streams, int warp_mode, double eps, int max
     if (rc) return fail(rc);
     if (hipMalloc((void **)&e->state, sizeof(EccState) * n_streams) != hipSuccess ||
         hipMalloc((void **)&e->d_warps, sizeof(float) * 6 * n_streams) != hipSuccess ||
+        hipMalloc((void **)&e->d_kept, sizeof(float) * 6 * n_streams) != hipSuccess ||
         hipMalloc((void **)&e->d_frame_off, sizeof(long long) * n_streams) != hipSuccess ||
         hipMalloc((void **)&e->d_frame_hw, sizeof(int) * 2 * n_streams) != hipSuccess ||
         hipHostMalloc((void **)&e->h_state, sizeof(EccState) * n_streams,
@@ -889,7 +924,8 @@ int yta_ecc_destroy(yta_ecc *e) {
     (void)hipSetDevice(e->device);
     if (e->stream) (void)host_wait(e->stream);
     ecc_free_slots(e);
-    for (void *p : {(void *)e->state, (void *)e->d_warps, (void *)e->d_frames,
+    cmc_tensors_free(e->t);
+    for (void *p : {(void *)e->state, (void *)e->d_warps, (void *)e->d_kept, (void *)e->d_frames,
                     (void *)e->d_frame_off, (void *)e->d_frame_hw, (void *)e->d_aligned})
         if (p) (void)hipFree(p);
     if (e->h_state) (void)hipHostFree(e->h_state);
@@ -914,6 +950,8 @@ int yta_ecc_apply_device(yta_ecc *e, const uint8_t *d_frames, const long long *d
     EccArgs &a = e->a;
     a.frames = d_frames;
     a.frame_off = d_frame_off;
+    a.frame_ptr = nullptr;
+    a.frame_pitch = nullptr;
     a.frame_hw = d_frame_hw;
     a.warps = d_warps;
     return ecc_launch(e);
@@ -946,23 +984,8 @@ int yta_ecc_apply(yta_ecc *e, const uint8_t *frames, const long long *frame_off,
         mh = std::max(mh, h);
         mw = std::max(mw, w);
     }
-    if (mh > e->max_h || mw > e->max_w) {
-        // grow the slots, keeping every stream's previous frame (packed from the slot start);
-        // on failure the engine keeps its previous slots and size untouched
-        YTA_HIP(host_wait(e->stream));
-        uint8_t *old = nullptr;
-        long long old_px = 0;
-        int rc = ecc_slots(e, mh, mw, &old, &old_px);
-        if (rc) return rc;
-        if (old) {
-            if (hipMemcpy2DAsync(e->img, e->a.slot_px, old, old_px, old_px, (size_t)S * 2,
-                                 hipMemcpyDeviceToDevice, e->stream) != hipSuccess ||
-                host_wait(e->stream) != hipSuccess)
-                rc = YTA_ERR_HIP;
-            (void)hipFree(old);
-        }
-        if (rc) return rc;
-    }
+    int rc = ecc_grow(e, mh, mw);
+    if (rc) return rc;
     if (bytes > e->frames_cap) {
         if (e->d_frames) (void)hipFree(e->d_frames);
         e->d_frames = nullptr;
@@ -975,11 +998,55 @@ int yta_ecc_apply(yta_ecc *e, const uint8_t *frames, const long long *frame_off,
                            e->stream));
     YTA_HIP(hipMemcpyAsync(e->d_frame_hw, frame_hw, sizeof(int) * 2 * S, hipMemcpyHostToDevice,
                            e->stream));
-    int rc = yta_ecc_apply_device(e, e->d_frames, e->d_frame_off, e->d_frame_hw, e->d_warps);
+    rc = yta_ecc_apply_device(e, e->d_frames, e->d_frame_off, e->d_frame_hw, e->d_warps);
     if (rc) return rc;
     YTA_HIP(hipMemcpyAsync(warps, e->d_warps, sizeof(float) * 6 * S, hipMemcpyDeviceToHost,
                            e->stream));
     return yta_ecc_sync(e);
+}
+
+int yta_ecc_apply_tensors(yta_ecc *e, void *caller_stream, const void *const *frames,
+                          const int *frame_hw, const long long *frame_pitch, float *d_warps) {
+    YTA_CHECK(e && d_warps, YTA_ERR_INVALID, "null argument");
+    YTA_HIP(hipSetDevice(e->device));
+    const int S = e->S;
+    const hipStream_t cs = (hipStream_t)caller_stream;
+    int rc = cmc_check_frames(S, cs, frames, frame_hw, frame_pitch);
+    if (rc) return rc;
+    int mh = e->max_h, mw = e->max_w;
+    for (int s = 0; s < S; ++s) {
+        mh = std::max(mh, frame_hw[2 * s]);
+        mw = std::max(mw, frame_hw[2 * s + 1]);
+    }
+    if (mh > e->max_h || mw > e->max_w) {
+        // sizes are known here: a frame whose warp tables cannot fit the LDS stage is refused
+        // before the engine stream is waited for or touched; any other larger frame grows the
+        // slots as yta_ecc_apply does
+        const long long hmax = std::llrint(mh * e->scale), wmax = std::llrint(mw * e->scale);
+        YTA_CHECK(8LL * (hmax + wmax) + 16 <= ECC_LDS, YTA_ERR_CAPACITY,
+                  "scaled frames of %lld x %lld: the warp tables exceed the LDS stage", hmax, wmax);
+        ++e->t.stat[CTS_HOST_WAITS];
+        rc = ecc_grow(e, mh, mw);
+        if (rc) return rc;
+    }
+    CmcSlot *slot = nullptr;
+    rc = cmc_hand_in(e->t, S, cs, e->stream, frames, frame_hw, frame_pitch, nullptr, &slot);
+    if (rc) return rc;
+    EccArgs &a = e->a;
+    a.frames = nullptr;
+    a.frame_off = nullptr;
+    a.frame_ptr = e->t.ptr;
+    a.frame_pitch = e->t.pitch;
+    a.frame_hw = e->t.hw;
+    a.warps = d_warps;
+    rc = ecc_launch(e);
+    if (rc) return rc;
+    return cmc_hand_back(slot, cs, e->stream);
+}
+
+int yta_ecc_tensor_stats(yta_ecc *e, long long *out, int n) {
+    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
+    return cmc_tensor_stats(e->t, out, n);
 }
 
 int yta_ecc_outcome(yta_ecc *e, int *outcome, int *iters, double *rho) {
@@ -1023,7 +1090,7 @@ int yta_ecc_aligned(yta_ecc *e, int stream, uint8_t *out, long long cap, int *h,
     YTA_HIP(hipMemcpy(&st, e->state + stream, sizeof(st), hipMemcpyDeviceToHost));
     *h = 0;
     *w = 0;
-    if (!st.init || st.outcome != ECC_OUT_EST || !e->a.warps) return YTA_OK;
+    if (!st.init || st.outcome != ECC_OUT_EST) return YTA_OK;
     const int slot = 1 - st.prev;
     const long long n = (long long)st.h[slot] * st.w[slot];
     YTA_CHECK(n > 0 && n <= e->a.slot_px, YTA_ERR_INVALID, "stream %d: bad template size", stream);

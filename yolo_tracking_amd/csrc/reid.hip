@@ -17,8 +17,11 @@
 // Output stores are nontemporal (the 393 KB per crop stream past L2; measured 1.14 -> 0.90 ms per
 // 8192-crop launch; -DYTA_REID_CACHED_STORES restores plain stores).
 //
-// Multi-image batches: box b reads image box_img[b] (HxWx3 uint8 BGR at imgs + img_off[i], dims
-// img_hw[2i], img_hw[2i+1]).  The kernel is HBM-write bound: each 128 x 256 crop writes 393 KB of
+// Multi-image batches: box b reads image box_img[b] (HxWx3 uint8 BGR, dims img_hw[2i],
+// img_hw[2i+1]): at imgs + img_off[i] with rows of 3 * w bytes (one packed allocation), or, in the
+// tensor form, at img_ptr[i] with rows img_pitch[i] bytes apart (a pointer table: separately
+// allocated, pitched or offset views; every source load is a byte load or an aligned dword).  Box
+// rows are float64 / float32 / float16, box_stride elements apart, promoted exactly.  The kernel is HBM-write bound: each 128 x 256 crop writes 393 KB of
 // float32 and reads a few KB of source pixels (which stay in L2).
 #include <hip/hip_fp16.h>
 
@@ -53,6 +56,11 @@ constexpr Lut make_lut() {
 }
 __constant__ Lut c_lut = make_lut();
 
+// A frame address read from a pointer table is a generic pointer to the compiler, which then emits
+// flat loads; frames are in global memory, and a pointer type that says so keeps the loads
+// global_load_*, as they are for a kernel-argument pointer.
+typedef __attribute__((address_space(1))) const uint8_t global_u8;
+
 struct Rect {
     int y0, y1, x0, x1;   // rows y0..y1-1, columns x0..x1-1; empty when y1 <= y0 or x1 <= x0
 };
@@ -85,8 +93,12 @@ __host__ __device__ inline Rect crop_rect(const double *box, int h, int w) {
 struct RpArgs {
     const uint8_t *imgs;
     const long long *img_off;
+    const uint8_t *const *img_ptr;   // nullable: the pointer table of the tensor form
+    const long long *img_pitch;      // with img_ptr: bytes between rows (>= 3 * w)
     const int *img_hw;
-    const double *boxes;
+    const void *boxes;    // rows x1 y1 x2 y2 of box_dtype, box_stride elements apart
+    int box_dtype;
+    long long box_stride;
     const int *box_img;   // nullable: every box reads image 0
     int n, out_h, out_w, half;
     void *out;
@@ -184,8 +196,29 @@ __global__ __launch_bounds__(RP_T) void k_reid_crops(RpArgs a) {
     const int b = blockIdx.x;
     const int img = a.box_img ? a.box_img[b] : 0;
     const int h = a.img_hw[2 * img], w = a.img_hw[2 * img + 1];
-    const uint8_t *base = a.imgs + a.img_off[img];
-    const Rect r = crop_rect(a.boxes + 4 * (long long)b, h, w);
+    global_u8 *base = (global_u8 *)(a.img_ptr ? a.img_ptr[img] : a.imgs + a.img_off[img]);
+    const int pitch = a.img_pitch ? (int)a.img_pitch[img] : 3 * w;   // < 2^31: one mad_i64_i32 a row
+    // the box row where the caller keeps it: one branch on the type, then four adjacent loads
+    double box[4];
+    const long long bi = (long long)b * a.box_stride;
+    if (a.box_dtype == YTA_F64) {
+        const double *p = static_cast<const double *>(a.boxes) + bi;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) box[q] = p[q];
+    } else if (a.box_dtype == YTA_F32) {
+        const float *p = static_cast<const float *>(a.boxes) + bi;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) box[q] = (double)p[q];
+    } else {
+        const _Float16 *p = static_cast<const _Float16 *>(a.boxes) + bi;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) box[q] = (double)p[q];
+    }
+    const Rect r = crop_rect(box, h, w);
+    // first byte of crop row y (crop-relative): the row's real address, whatever the pitch
+    auto crop_row = [&](int y) -> global_u8 * {
+        return base + (long long)(r.y0 + y) * pitch + r.x0 * 3;
+    };
     const int ch = r.y1 - r.y0, cw = r.x1 - r.x0;
     const int OW = a.out_w, OH = a.out_h;
     const long long plane = (long long)OH * OW;
@@ -215,8 +248,8 @@ __global__ __launch_bounds__(RP_T) void k_reid_crops(RpArgs a) {
         for (int e = threadIdx.x; e < nrows * groups; e += RP_T) {
             const int ry = e / groups, dy = row0 + ry, dx0 = (e - ry * groups) * V;
             float res[3][V];
-            const uint8_t *p0 = base + ((long long)(r.y0 + 2 * dy) * w + r.x0) * 3;
-            const uint8_t *p1 = p0 + (long long)w * 3;
+            global_u8 *p0 = crop_row(2 * dy);
+            global_u8 *p1 = p0 + pitch;
 #pragma unroll
             for (int k = 0; k < V; ++k) {
                 const int sx = 2 * (dx0 + k);
@@ -268,7 +301,7 @@ __global__ __launch_bounds__(RP_T) void k_reid_crops(RpArgs a) {
         __syncthreads();                                  // x tables
         for (int e = threadIdx.x; e < R * groups; e += RP_T) {
             const int rr = e / groups, dx0 = (e - rr * groups) * V;
-            const uint8_t *q = base + ((long long)(r.y0 + lo + rr) * w + r.x0) * 3;
+            global_u8 *q = crop_row(lo + rr);
             short o[3][4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -319,13 +352,20 @@ __global__ __launch_bounds__(RP_T) void k_reid_crops(RpArgs a) {
     const int rs = ((cw * 3 + 3 + 3) / 4) * 4;   // LDS stride: the row's dword run
     const bool staged = R <= STAGE_ROWS && (long long)R * rs <= STAGE_BYTES;
     if (staged) {   // dword-aligned runs covering each row's cw * 3 bytes, coalesced
+        // The run starts at the aligned dword holding the row's first byte: s_lead is taken from
+        // the row's real address, so a pitch or base of any alignment gives aligned dword loads.
+        // A run may end past the row's last byte by up to 7 bytes that nothing reads; dwords
+        // wholly past the image's last byte are not loaded (a frame tensor may end its allocation).
         const int ndw = rs / 4;
+        const uintptr_t img_end = (uintptr_t)(base + (long long)(h - 1) * pitch + w * 3);
         for (int e = threadIdx.x; e < R * ndw; e += RP_T) {
             const int rr = e / ndw, k = e - rr * ndw;
-            const uint8_t *rp = base + ((long long)(r.y0 + lo + rr) * w + r.x0) * 3;
+            global_u8 *rp = crop_row(lo + rr);
             const uintptr_t al = (uintptr_t)rp & ~(uintptr_t)3;
             if (k == 0) s_lead[rr] = (int)((uintptr_t)rp - al);
-            reinterpret_cast<unsigned *>(s_rows + rr * rs)[k] = ((const unsigned *)al)[k];
+            typedef __attribute__((address_space(1))) const unsigned global_u32;
+            global_u32 *src = (global_u32 *)al + k;
+            reinterpret_cast<unsigned *>(s_rows + rr * rs)[k] = (uintptr_t)src < img_end ? *src : 0u;
         }
     }
     __syncthreads();
@@ -341,8 +381,7 @@ __global__ __launch_bounds__(RP_T) void k_reid_crops(RpArgs a) {
             const uint8_t *q1 = s_rows + (y1 - lo) * rs + s_lead[y1 - lo];
             bilinear_group<V>(q0, q1, dx0, b0, b1, cw, s_sx, s_a, s_lut, res);
         } else {
-            const uint8_t *q0 = base + ((long long)(r.y0 + y0) * w + r.x0) * 3;
-            const uint8_t *q1 = base + ((long long)(r.y0 + y1) * w + r.x0) * 3;
+            global_u8 *q0 = crop_row(y0), *q1 = crop_row(y1);
             bilinear_group<V>(q0, q1, dx0, b0, b1, cw, s_sx, s_a, s_lut, res);
         }
         store_group<V>(a.out, obase, plane, dy, OW, dx0, res, a.half);
@@ -464,8 +503,9 @@ int yta_reid_preprocess(int device, const uint8_t *img, int h, int w, const doub
     YTA_HIP(hipMemcpy(d_boxes, xyxys, sizeof(double) * 4 * n, hipMemcpyHostToDevice));
     YTA_HIP(hipMemcpy(d_meta, &off0, 8, hipMemcpyHostToDevice));
     YTA_HIP(hipMemcpy((char *)d_meta + 8, hw, 8, hipMemcpyHostToDevice));
-    RpArgs a{(const uint8_t *)d_img, (const long long *)d_meta, (const int *)((char *)d_meta + 8),
-             (const double *)d_boxes, nullptr, n, out_h, out_w, half, d_out, nullptr};
+    RpArgs a{(const uint8_t *)d_img, (const long long *)d_meta, nullptr, nullptr,
+             (const int *)((char *)d_meta + 8), d_boxes, YTA_F64, 4, nullptr, n, out_h, out_w, half,
+             d_out, nullptr};
     rc = launch_crops(a, 0);
     if (rc) return rc;
     YTA_HIP(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
@@ -481,8 +521,28 @@ int yta_reid_preprocess_device(const uint8_t *d_imgs, const long long *d_img_off
     if (n == 0) return YTA_OK;
     YTA_CHECK(d_imgs && d_img_off && d_img_hw && d_xyxys && d_out, YTA_ERR_INVALID,
               "null buffer");
-    RpArgs a{d_imgs, d_img_off, d_img_hw, d_xyxys, d_box_img, n, out_h, out_w, half, d_out,
-             d_n_empty};
+    RpArgs a{d_imgs, d_img_off, nullptr, nullptr, d_img_hw, d_xyxys, YTA_F64, 4, d_box_img, n,
+             out_h, out_w, half, d_out, d_n_empty};
+    return launch_crops(a, (hipStream_t)stream);
+}
+
+int yta_reid_preprocess_tensors(const void *const *d_frames, const int *d_img_hw,
+                                const long long *d_img_pitch, const void *d_boxes, int dtype,
+                                long long row_stride, const int *d_box_img, int n, int out_h,
+                                int out_w, int half, void *d_out, int *d_n_empty, void *stream) {
+    YTA_CHECK(n >= 0 && (half == 0 || half == 1), YTA_ERR_INVALID, "bad arguments (n %d, half %d)",
+              n, half);
+    YTA_CHECK(dtype == YTA_F64 || dtype == YTA_F32 || dtype == YTA_F16, YTA_ERR_INVALID,
+              "dtype %d is none of YTA_F64, YTA_F32, YTA_F16", dtype);
+    YTA_CHECK(row_stride >= 4, YTA_ERR_INVALID, "row_stride %lld < 4", row_stride);
+    if (n == 0) return YTA_OK;
+    YTA_CHECK(d_frames && d_img_hw && d_img_pitch && d_boxes && d_out, YTA_ERR_INVALID,
+              "null buffer");
+    const size_t esz = dtype == YTA_F64 ? 8 : dtype == YTA_F32 ? 4 : 2;
+    YTA_CHECK((uintptr_t)d_boxes % esz == 0, YTA_ERR_INVALID,
+              "d_boxes not aligned to its element size");
+    RpArgs a{nullptr, nullptr, (const uint8_t *const *)d_frames, d_img_pitch, d_img_hw, d_boxes,
+             dtype, row_stride, d_box_img, n, out_h, out_w, half, d_out, d_n_empty};
     return launch_crops(a, (hipStream_t)stream);
 }
 

@@ -70,6 +70,29 @@ class EccEngine:
                                           _lib.ptr(self._warps)))
         return self._warps.reshape(self.n_streams, 2, 3).copy()
 
+    def apply_tensors(self, frames, stream=None):
+        """The tensor form of apply (yta_ecc_apply_tensors): frames as SofEngine.apply_tensors
+        takes them, read where they are; returns an (S, 2, 3) float32 CUDA tensor ordered on
+        `stream` (default: the current stream), with no host wait."""
+        import torch
+        from ..trackers._tensors import frame_table
+        S, dev = self.n_streams, self.device
+        keep, ptr, hw, pitch = frame_table(frames, S, dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        with torch.cuda.stream(stream):
+            warps = torch.empty((S, 6), dtype=torch.float32, device=keep[0].device)
+        _lib.check(self.lib.yta_ecc_apply_tensors(
+            self._h, ctypes.c_void_p(stream.cuda_stream), _lib.ptr(ptr), _lib.ptr(hw),
+            _lib.ptr(pitch), ctypes.c_void_p(warps.data_ptr())))
+        return warps.view(S, 2, 3)
+
+    def tensor_stats(self):
+        """Accounting of apply_tensors: frames enqueued, calls that blocked on the device."""
+        buf = (ctypes.c_longlong * 2)()
+        _lib.check(self.lib.yta_ecc_tensor_stats(self._h, buf, 2))
+        return {"frames": int(buf[0]), "host_waits": int(buf[1])}
+
     def outcome(self):
         """Per stream (outcome, iterations, rho): outcome 0 first frame, 1 estimated, 2 identity
         (findTransformECC would have raised)."""
@@ -134,12 +157,17 @@ class ECC:
         self._engine = None
 
     def apply(self, img, dets=None):
-        img = np.asarray(img)
+        """A CUDA `img` is read where it is and the warp comes back as a CUDA (2, 3) float32
+        tensor; NumPy in gives NumPy out.  align=True works with both (aligned() waits)."""
+        from ..trackers._tensors import is_cuda_tensor
+        on_device = is_cuda_tensor(img)
+        if not on_device:
+            img = np.asarray(img)
         if self._engine is None:
             _, max_iter, eps = self.termination_criteria
             self._engine = EccEngine(1, self.warp_mode, eps, max_iter, self.scale, self._device,
                                      img.shape[0], img.shape[1])
-        warp = self._engine.apply([img])[0]
+        warp = (self._engine.apply_tensors([img]) if on_device else self._engine.apply([img]))[0]
         if self.align:   # after an estimate only: the other paths return before ecc.py:91
             aligned = self._engine.aligned(0)
             if aligned is not None:

@@ -6,6 +6,9 @@ float64 warp; the work runs in csrc/cmc.hip (gray + resize, goodFeaturesToTrack 
 pyramidal Lucas-Kanade, RANSAC + LM similarity fit) through the C ABI.  `SofEngine` runs S camera
 streams per call (every stream's frame in the same launches); its device form writes the S warps
 straight into a device buffer that yta_botsort_update_device / yta_deepocsort_update_device read.
+`SofEngine.apply_tensors` takes the frames and the detection rows as CUDA tensors where they are
+(yta_sof_apply_tensors: stream-ordered, nothing crosses the link, no host wait) and returns the
+warps as a CUDA tensor; `SparseOptFlow.apply` goes that way when `img` is a CUDA tensor.
 There is no CPU fallback: without the HIP library or a device this raises YTAError.
 """
 import ctypes
@@ -74,6 +77,49 @@ class SofEngine:
                                           _lib.ptr(self._warps)))
         return self._warps.reshape(self.n_streams, 2, 3).copy()
 
+    def apply_tensors(self, frames, dets=None, counts=None, conf_thresh=None, stream=None):
+        """The tensor form of apply (yta_sof_apply_tensors).  frames: a list of S CUDA uint8
+        (h, w, 3) tensors with strides (pitch, 3, 1), or one (S, h, w, 3) tensor (frame_table in
+        trackers/_tensors.py).  dets: a list of S CUDA tensors (n_s, >= 4) of float64 / float32 /
+        float16, or one packed tensor with `counts` (TensorFrame's conventions); x1 y1 x2 y2
+        [conf] come first, a column slice of a wider tensor is read in place; None: no boxes.
+        conf_thresh: only rows with conf (column 4) > conf_thresh enter the mask, chosen on the
+        device.  Returns an (S, 2, 3) float64 CUDA tensor, ordered on `stream` (default: the
+        current stream): the inputs may be overwritten right after the call."""
+        import torch
+        from ..trackers import _tensors as T
+        S, dev = self.n_streams, self.device
+        keep, ptr, hw, pitch = T.frame_table(frames, S, dev)
+        need = 4 if conf_thresh is None else 5
+        if dets is None:
+            dets, counts = torch.zeros((0, need), dtype=torch.float64,
+                                       device=keep[0].device), [0] * S
+        first = dets[0] if isinstance(dets, (list, tuple)) and len(dets) else dets
+        cols = first.shape[1] if isinstance(first, torch.Tensor) and first.dim() == 2 else need
+        if cols < need:
+            raise ValueError(f"dets: {cols} columns, x1 y1 x2 y2"
+                             f"{' conf' if need == 5 else ''} are needed")
+        codes = T._dtype_codes(torch)
+        rows, cnt = T._rows(torch, dets, counts, S, "dets", dev, cols, tuple(codes))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        with torch.cuda.stream(stream):
+            rows, row_stride = T._pack(torch, rows, need)
+            warps = torch.empty((S, 6), dtype=torch.float64, device=keep[0].device)
+        th = None if conf_thresh is None else ctypes.byref(ctypes.c_double(float(conf_thresh)))
+        _lib.check(self.lib.yta_sof_apply_tensors(
+            self._h, ctypes.c_void_p(stream.cuda_stream), _lib.ptr(ptr), _lib.ptr(hw),
+            _lib.ptr(pitch), ctypes.c_void_p(rows.data_ptr()) if rows.numel() else None,
+            codes[rows.dtype], int(row_stride), _lib.ptr(cnt), th,
+            ctypes.c_void_p(warps.data_ptr())))
+        return warps.view(S, 2, 3)
+
+    def tensor_stats(self):
+        """Accounting of apply_tensors: frames enqueued, calls that blocked on the device."""
+        buf = (ctypes.c_longlong * 2)()
+        _lib.check(self.lib.yta_sof_tensor_stats(self._h, buf, 2))
+        return {"frames": int(buf[0]), "host_waits": int(buf[1])}
+
     def outcome(self):
         """Per stream: 0 first frame, 1 estimated, 2 identity (see yta_sof_outcome)."""
         out = np.zeros(self.n_streams, np.int32)
@@ -99,7 +145,9 @@ class SofEngine:
 class SparseOptFlow:
     """Drop-in for boxmot.motion.cmc.sof.SparseOptFlow (sof.py:15-61): same constructor
     arguments (warp_mode / eps / max_iter / align / grayscale / draw_optical_flow are accepted
-    and, as in the reference, unused by apply), `apply(img, dets) -> 2x3 float64`."""
+    and, as in the reference, unused by apply), `apply(img, dets) -> 2x3 float64`.  A CUDA `img`
+    (uint8 (h, w, 3), rows any pitch >= 3 * w) is read where it is and the warp comes back as a
+    CUDA (2, 3) tensor (dets then NumPy or CUDA); NumPy in gives NumPy out."""
 
     def __init__(self, warp_mode=None, eps=1e-5, max_iter=100, scale=0.1, align=False,
                  grayscale=True, draw_optical_flow=False, device=0):
@@ -114,6 +162,17 @@ class SparseOptFlow:
         self._engine = None
 
     def apply(self, img, dets):
+        from ..trackers._tensors import is_cuda_tensor
+        if is_cuda_tensor(img):
+            import torch
+            if self._engine is None:
+                self._engine = SofEngine(1, self.scale, self._device, img.shape[0], img.shape[1])
+            if dets is not None and not is_cuda_tensor(dets):
+                d = np.asarray(dets, dtype=np.float64)
+                dets = torch.from_numpy(d.reshape(len(d), -1)).to(img.device) if d.size else None
+            elif dets is not None and dets.shape[0] == 0:
+                dets = None
+            return self._engine.apply_tensors([img], None if dets is None else [dets])[0]
         img = np.asarray(img)
         if self._engine is None:
             self._engine = SofEngine(1, self.scale, self._device, img.shape[0], img.shape[1])

@@ -180,3 +180,51 @@ class TensorPath:
         """Wait for the engine's stream; raises if a frame since the last wait set a device
         error flag."""
         self._call("sync")
+
+
+def frame_table(frames, n_streams, device, name="frames"):
+    """The pointer table of S device frames for yta_sof_apply_tensors / yta_ecc_apply_tensors /
+    yta_reid_preprocess_tensors: `frames` is a list of S CUDA uint8 (h, w, 3) tensors with strides
+    (pitch, 3, 1), pitch >= 3 * w (contiguous frames, pitched decoder surfaces, offset views,
+    slices of a batch tensor), or one (S, h, w, 3) tensor.  Returns (frames, addresses (S uint64),
+    hw (2 S int32), pitch (S int64)); the frames are returned so the caller keeps them alive.
+    Checks only: nothing is copied and no value is read from the device."""
+    import torch
+    if isinstance(frames, torch.Tensor):
+        if frames.dim() != 4:
+            raise ValueError(f"{name}: one tensor must be (S, h, w, 3), got {tuple(frames.shape)}")
+        frames = list(frames.unbind(0))
+    if not isinstance(frames, (list, tuple)) or len(frames) != n_streams:
+        n = len(frames) if isinstance(frames, (list, tuple)) else type(frames).__name__
+        raise ValueError(f"{name}: {n} frames for {n_streams} streams")
+    ptr = np.zeros(n_streams, dtype=np.uint64)
+    hw = np.zeros(2 * n_streams, dtype=np.int32)
+    pitch = np.zeros(n_streams, dtype=np.int64)
+    for s, f in enumerate(frames):
+        who = f"{name}[{s}]"
+        if not isinstance(f, torch.Tensor):
+            raise ValueError(f"{who}: expected a torch tensor, got {type(f).__name__}")
+        if not f.is_cuda or f.device.index != device:
+            raise ValueError(f"{who}: tensor on {f.device}, the engine runs on cuda:{device}")
+        if f.dtype != torch.uint8:
+            raise ValueError(f"{who}: dtype {f.dtype}, frames are uint8 BGR")
+        if f.dim() != 3 or f.shape[2] != 3 or f.shape[0] < 1 or f.shape[1] < 1:
+            raise ValueError(f"{who}: expected shape (h, w, 3), got {tuple(f.shape)}")
+        h, w = int(f.shape[0]), int(f.shape[1])
+        if f.stride(2) != 1 or (w > 1 and f.stride(1) != 3):
+            raise ValueError(f"{who}: strides {f.stride()}: the channels must be adjacent and "
+                             "the pixels 3 bytes apart (interleaved BGR)")
+        p = int(f.stride(0)) if h > 1 else max(int(f.stride(0)), 3 * w)
+        if p < 3 * w:
+            raise ValueError(f"{who}: row pitch {p} below 3 * w = {3 * w}")
+        ptr[s], hw[2 * s], hw[2 * s + 1], pitch[s] = f.data_ptr(), h, w, p
+    return list(frames), ptr, hw, pitch
+
+
+def takes_device_frames(obj):
+    """True for this package's own producers (ReIDDetectMultiBackend, SparseOptFlow, ECC,
+    IdentityCMC), which take a CUDA frame and CUDA boxes where they are.  Any other `reid=` /
+    `cmc=` object is handed a NumPy frame and NumPy rows, as the reference's interface has it."""
+    from ..appearance.reid_multibackend import ReIDDetectMultiBackend
+    from ..motion.cmc import ECC, IdentityCMC, SparseOptFlow
+    return isinstance(obj, (ReIDDetectMultiBackend, SparseOptFlow, ECC, IdentityCMC))

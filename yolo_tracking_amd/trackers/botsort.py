@@ -21,7 +21,7 @@ import numpy as np
 from .. import _lib
 from ..appearance import build_reid
 from ..motion.cmc import IdentityCMC, default_cmc
-from ._tensors import is_cuda_tensor
+from ._tensors import is_cuda_tensor, takes_device_frames
 from .bytetrack import ByteTrackEngine, STrackView
 
 
@@ -231,19 +231,46 @@ class BoTSORT:
 
     def _update_tensor(self, dets, img, embs):
         """update() for a CUDA tensor of detections (embs, when given, a CUDA tensor with one row
-        per detection): the embeddings and the rows stay on the device.  Only the high boxes go
-        to the host, for the crops and the camera-motion estimate, which take host frames."""
+        per detection): the embeddings and the rows stay on the device.  With a CUDA `img` (uint8
+        (h, w, 3), rows any pitch >= 3 * w) nothing crosses the link: the high rows stay in HBM,
+        the crops and the camera-motion estimate read the frame and the rows where they are
+        (ReIDDetectMultiBackend.get_features, SparseOptFlow / ECC.apply), and the warp goes to the
+        engine as a device tensor.  A caller-supplied `reid=` or `cmc=` object that is not this
+        package's gets `img.cpu().numpy()` (one download per call) and NumPy rows.  With a NumPy
+        `img` the high boxes go to the host, for the crops and the estimate, as before."""
         import torch
-        assert isinstance(img, np.ndarray), \
+        img_dev = is_cuda_tensor(img)
+        assert img_dev or isinstance(img, np.ndarray), \
             f"Unsupported 'img_numpy' input format '{type(img)}', valid format is np.ndarray"
         assert dets.dim() == 2, "Unsupported 'dets' dimensions, valid number of dimensions is two"
         assert dets.shape[1] == 6, "Unsupported 'dets' 2nd dimension lenght, valid lenghts is 6"
         self.frame_id += 1
         # compared as float64, like the engine and the ndarray path (:266-267)
         high = dets[:, 4].double() > self.track_high_thresh
-        high_rows = dets[high].double().cpu().numpy()
+        img_host = None if img_dev else img
+
+        def host_img():   # for a foreign reid / cmc object: one download per call
+            nonlocal img_host
+            if img_host is None:
+                img_host = img.cpu().numpy()
+            return img_host
+
+        if img_dev:
+            high_dev = dets[high]               # the one wait of the call: K
+            high_rows = None
+        else:
+            high_dev = None
+            high_rows = dets[high].double().cpu().numpy()
+
+        def host_rows():
+            nonlocal high_rows
+            if high_rows is None:
+                high_rows = high_dev.double().cpu().numpy()
+            return high_rows
+
+        n_high = high_dev.shape[0] if img_dev else len(high_rows)
         feats = None
-        if self.with_reid and len(high_rows):                    # :270-271
+        if self.with_reid and n_high:                            # :270-271
             if embs is not None:
                 if not is_cuda_tensor(embs) or embs.dim() != 2 or len(embs) != len(dets):
                     raise ValueError("embs: with tensor dets, a CUDA tensor with one row per "
@@ -256,17 +283,25 @@ class BoTSORT:
                         "get_features(xyxys, img)> or update(dets, img, embs=...)")
                 # ReIDDetectMultiBackend keeps them in HBM; a producer without as_tensor hands
                 # NumPy rows, which are uploaded
-                if "as_tensor" in inspect.signature(self.model.get_features).parameters:
-                    f = self.model.get_features(high_rows[:, 0:4], img, as_tensor=True).float()
+                if img_dev and takes_device_frames(self.model):
+                    f = self.model.get_features(high_dev[:, 0:4], img, as_tensor=True).float()
+                elif "as_tensor" in inspect.signature(self.model.get_features).parameters:
+                    f = self.model.get_features(host_rows()[:, 0:4], host_img(),
+                                                as_tensor=True).float()
                 else:
                     f = torch.from_numpy(np.asarray(self.model.get_features(
-                        high_rows[:, 0:4], img), np.float32)).to(dets.device)
+                        host_rows()[:, 0:4], host_img()), np.float32)).to(dets.device)
                 feats = torch.zeros((len(dets), f.shape[1]), dtype=torch.float32,
                                     device=dets.device)
                 feats[high] = f
             if self._engine is None:
                 self._make_engine(feats.shape[1])
-        warp = np.asarray(self.cmc.apply(img, high_rows), dtype=np.float64)   # :299
+        if img_dev and takes_device_frames(self.cmc):            # :299, the warp stays in HBM
+            w = self.cmc.apply(img, high_dev)
+            warp = w.double().reshape(1, 2, 3) if is_cuda_tensor(w) \
+                else np.asarray(w, dtype=np.float64)[None]
+        else:
+            warp = np.asarray(self.cmc.apply(host_img(), host_rows()), dtype=np.float64)[None]
         if self._engine is None:                                  # no high detection yet
             self._empty_frames += 1
             return dets.new_zeros((0, 8), dtype=torch.float64)
@@ -274,8 +309,7 @@ class BoTSORT:
             feats = torch.zeros((len(dets), self._engine.feat_dim), dtype=torch.float32,
                                 device=dets.device)
         self._nid[0] = BaseTrack._count
-        rows, off, _ = self._engine.update_tensors([dets], feats, warps=warp[None],
-                                                   next_id=self._nid)
+        rows, off, _ = self._engine.update_tensors([dets], feats, warps=warp, next_id=self._nid)
         BaseTrack._count = int(self._engine.next_ids()[0])   # waits: the frame has run
         return rows[:int(off[1])]
 

@@ -20,7 +20,7 @@ import numpy as np
 
 from .. import _lib
 from ._streams import StreamSubset
-from ._tensors import TensorFrame, TensorPath, is_cuda_tensor
+from ._tensors import TensorFrame, TensorPath, is_cuda_tensor, takes_device_frames
 from ..appearance import build_reid
 from ..motion.cmc import default_cmc
 
@@ -288,11 +288,17 @@ class DeepOCSort:
 
     def _update_tensor(self, dets, img, embs):
         """update() for a CUDA tensor of detections (embs, when given, a CUDA tensor with one row
-        per detection): the embeddings and the rows stay on the device.  Only the kept boxes go
-        to the host, for the crops and the camera-motion estimate, which take host frames.  One
-        wait per call, to learn K and to keep the process-global KalmanBoxTracker.count."""
+        per detection): the embeddings and the rows stay on the device.  With a CUDA `img` (uint8
+        (h, w, 3), rows any pitch >= 3 * w) nothing crosses the link: the kept rows stay in HBM,
+        the crops and the camera-motion estimate read the frame and the rows where they are
+        (ReIDDetectMultiBackend.get_features, SparseOptFlow / ECC.apply), and the warp goes to the
+        engine as a device tensor.  A caller-supplied `reid=` or `cmc=` object that is not this
+        package's gets `img.cpu().numpy()` (one download per call) and NumPy rows.  With a NumPy
+        `img` the kept boxes go to the host, for the crops and the estimate, as before.  One wait
+        per call, to learn K and to keep the process-global KalmanBoxTracker.count."""
         import torch
-        assert isinstance(img, np.ndarray), \
+        img_dev = is_cuda_tensor(img)
+        assert img_dev or isinstance(img, np.ndarray), \
             f"Unsupported 'img' input type '{type(img)}', valid format is np.ndarray"
         assert dets.dim() == 2, "Unsupported 'dets' dimensions, valid number of dimensions is two"
         assert dets.shape[1] == 6, "Unsupported 'dets' 2nd dimension lenght, valid lenghts is 6"
@@ -301,8 +307,25 @@ class DeepOCSort:
         keep = dets[:, 4].double() > self.det_thresh
         need_boxes = (not self.embedding_off and embs is None) or \
             (not self.cmc_off and self.cmc is not None)
-        kept_rows = dets[keep].double().cpu().numpy() if need_boxes else None
-        n_kept = len(kept_rows) if need_boxes else int(keep.sum())
+        img_host = None if img_dev else img
+
+        def host_img():   # for a foreign reid / cmc object: one download per call
+            nonlocal img_host
+            if img_host is None:
+                img_host = img.cpu().numpy()
+            return img_host
+
+        kept_dev = dets[keep] if need_boxes and img_dev else None   # the wait for K
+        kept_rows = dets[keep].double().cpu().numpy() if need_boxes and not img_dev else None
+
+        def host_rows():
+            nonlocal kept_rows
+            if kept_rows is None:
+                kept_rows = kept_dev.double().cpu().numpy()
+            return kept_rows
+
+        n_kept = (kept_dev.shape[0] if img_dev else len(kept_rows)) if need_boxes \
+            else int(keep.sum())
         feats = None
         if not self.embedding_off and n_kept:                        # :383-387
             if embs is not None:
@@ -317,11 +340,14 @@ class DeepOCSort:
                         "get_features(xyxys, img)> or update(dets, img, embs=...)")
                 # ReIDDetectMultiBackend keeps them in HBM; a producer without as_tensor hands
                 # NumPy rows, which are uploaded
-                if "as_tensor" in inspect.signature(self.model.get_features).parameters:
-                    f = self.model.get_features(kept_rows[:, 0:4], img, as_tensor=True).float()
+                if img_dev and takes_device_frames(self.model):
+                    f = self.model.get_features(kept_dev[:, 0:4], img, as_tensor=True).float()
+                elif "as_tensor" in inspect.signature(self.model.get_features).parameters:
+                    f = self.model.get_features(host_rows()[:, 0:4], host_img(),
+                                                as_tensor=True).float()
                 else:
                     f = torch.from_numpy(np.asarray(self.model.get_features(
-                        kept_rows[:, 0:4], img), np.float32)).to(dets.device)
+                        host_rows()[:, 0:4], host_img()), np.float32)).to(dets.device)
                 feats = torch.zeros((len(dets), f.shape[1]), dtype=torch.float32,
                                     device=dets.device)
                 feats[keep] = f
@@ -329,7 +355,13 @@ class DeepOCSort:
                 self._make_engine(feats.shape[1])
         warp = None
         if not self.cmc_off and self.cmc is not None:                # :390-393
-            warp = np.asarray(self.cmc.apply(img, kept_rows[:, :4]), dtype=np.float64)[None]
+            if img_dev and takes_device_frames(self.cmc):            # the warp stays in HBM
+                w = self.cmc.apply(img, kept_dev[:, :4])
+                warp = w.double().reshape(1, 2, 3) if is_cuda_tensor(w) \
+                    else np.asarray(w, dtype=np.float64)[None]
+            else:
+                warp = np.asarray(self.cmc.apply(host_img(), host_rows()[:, :4]),
+                                  dtype=np.float64)[None]
         if self._engine is None:                                     # no kept detection yet
             self._empty_frames += 1
             return dets.new_zeros((0, 8), dtype=torch.float64)
@@ -337,8 +369,8 @@ class DeepOCSort:
             feats = torch.zeros((len(dets), self._engine.feat_dim), dtype=torch.float32,
                                 device=dets.device)
         self._nid[0] = KalmanBoxTracker.count
-        rows, off, _ = self._engine.update_tensors([dets], feats, warps=warp,
-                                                   img_shapes=[img.shape], next_id=self._nid)
+        rows, off, _ = self._engine.update_tensors([dets], feats, warps=warp, next_id=self._nid,
+                                                   img_shapes=[tuple(img.shape)])
         KalmanBoxTracker.count = int(self._engine.next_ids()[0])   # waits: the frame has run
         return rows[:int(off[1])]
 
