@@ -109,6 +109,18 @@ int yta_selftest(int device);
  * works on; both arrays hold gx * n_streams ints. */
 int yta_apply_block_map(int gx, int n_streams, int *stream, int *block);
 
+/* Host evaluation (no device needed) of the conservative pre-tests ByteTrack's k_s1_edges puts in
+ * front of its float64 IoU (csrc/grid.hpp: box_pack16, box16_meet), with origin and scale derived
+ * as the kernel derives them from the stream's high detections.
+ * pool: nr boxes x1,y1,x2,y2; high / score: nc boxes and scores; thresh: match_thresh.
+ * out[i * nc + j]: bit 0 = the packed boxes of pool row i and detection j meet; bit 1 = the pair
+ * also passes the second stage (a bound on IoU x score against 1 - thresh), which was measured
+ * and not kept: the kernel has none, every pair that meets passes, bit 1 = bit 0
+ * and score / thresh are not read.  3 for a detection that is not binned (unusable or larger than
+ * 4 x the mean size: the kernel tests those pairs in float64 only). */
+int yta_s1_pretest(int nr, const double *pool, int nc, const double *high, const double *score,
+                   double thresh, unsigned char *out);
+
 /* ---- linear assignment with lapx cost_limit semantics -------------------------------------
  * Minimises sum(matched cost) + cost_limit/2 * (#unmatched rows + #unmatched cols); x[r] = col or
  * -1, y[c] = row or -1 (lap.lapjv(cost, extend_cost=True, cost_limit=cost_limit)). */

@@ -157,6 +157,7 @@ _SIGS = {
     "yta_hybridsort_next_ids": ([_P, _P], _I),
     "yta_selftest": ([_I], _I),
     "yta_apply_block_map": ([_I, _I, _P, _P], _I),
+    "yta_s1_pretest": ([_I, _P, _I, _P, _P, _D, _P], _I),
     "yta_botsort_create": ([_I, _I, _I, _I, _I, _P, _P], _I),
     "yta_botsort_update": ([_P, _P, _P, _P, _P, _P, _P, _I, _P], _I),
     "yta_botsort_update_device": ([_P, _P, _P, _P, _P, _P, _P], _I),

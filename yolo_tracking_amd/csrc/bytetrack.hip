@@ -518,7 +518,7 @@ __global__ __launch_bounds__(SPLIT ? BLK23S : BLK23) void k_redo_stage23(BtArgs 
 // LDS only do not drain global stores (lds_sync).  (The pool = act ++ lost with predicted boxes,
 // :169-178, is built by the previous frame's k_finish, or by k_pool_build after a reserve.  The
 // detection pass had a launch of its own, k_s1_prep, up to DESIGN 13.10; commit 15db9ac has it.)
-//   k_s1_edges [block/stream, 512 thr, <= 62 KiB LDS] the detection pass and confidence split
+//   k_s1_edges [block/stream, 512 thr, <= 63 KiB LDS] the detection pass and confidence split
 //              (:149-158) from registers (s1_dets_fused: two rows per thread, one packed scan,
 //              lists to HBM, the high boxes handed to their list positions' threads through LDS),
 //              the grid over the high detections built in LDS from those registers, then every
@@ -794,9 +794,12 @@ __device__ __forceinline__ GridView s1_grid_hbm(const BtArgs &a, int s) {
                     a.g_boxes + db, a.g_w + db, a.g_big + db};
 }
 
-// LDS bytes of a grid over C detections in k_s1_edges.
+// LDS bytes of a grid over C detections in k_s1_edges: cell_start, then per detection the 16-bit
+// id (the big list shares that array, GridView::ids16), the float64 box (sx), the score and the
+// packed box (GridView::pk); 5 * 16 covers the arena's rounding of six allocations to 16 B (at
+// most 12 + 14 + 0 + 8 + 8 + 12 with cdeg, which the dispatch condition adds as 4 C).
 __host__ __device__ inline long long s1_grid_bytes(long long C) {
-    return 4 * (GRID_MAX_CELLS + 1) + C * (4 + 32 + 8 + 4) + 5 * 16;
+    return 4 * (GRID_MAX_CELLS + 1) + C * (2 + 32 + 8 + 8) + 5 * 16;
 }
 
 // k_s1_edges body over a grid whose storage (LDS or HBM) the caller fixed: inlined once per
@@ -851,9 +854,13 @@ __device__ __forceinline__ void s1_edges_body(const BtArgs &a, int s, int nc, in
 // grid positions (no LDS bank conflicts from 64 scattered 32-B boxes).  A row's box reaches the
 // lane scoring its candidate by ds_bpermute.  Edges land in per-row LDS counters; their order
 // within a row does not matter (lap_block, the single-edge pass and k_s1_lap's re-query are
-// order-free).  Queues hold WQ_CAP entries; a larger candidate total is listed and scored in
-// windows.  Big items (larger than 4 x the mean box) are visited per lane, as grid_query does.
-constexpr int WQ_CAP = 384;
+// order-free).  Queues hold WQ_CAP 16-bit entries (a wave of the headline lists ~400 candidates:
+// with 384 32-bit entries many took a second window, listing loop included); a
+// larger candidate total is listed and scored in windows.  Big items (larger than 4 x the mean
+// box) are visited per lane, as grid_query does.
+constexpr int WQ_CAP = 768;
+constexpr int WQ_POS_BITS = 10;   // a queue entry is 16 bits: lane << 10 | grid position, so the
+                                  // LDS grid holds at most 1024 detections (k_s1_edges' dispatch)
 // The LDS grid keeps its boxes as four arrays (GridView::sx): conflict-free wave reads.  The
 // array-of-boxes layout and the one-chunk, short-circuit queue passes
 // lost their A/Bs and were removed; commit 15db9ac has them.
@@ -863,9 +870,9 @@ __device__ __forceinline__ Box s1_box(const GridView &gv, int k) {
     return Box{x[k], x[n + k], x[2 * n + k], x[3 * n + k]};
 }
 struct EdgeWaveQ {
-    unsigned q[WQ_CAP];   // lane << 24 | grid position
+    unsigned short q[WQ_CAP];   // lane << WQ_POS_BITS | grid position
     int cnt[WAVE];        // edges of the wave's row `lane`
-    int first[WAVE];      // its first edge's detection
+    unsigned short first[WAVE];   // its first edge's detection (only read when cnt is 1)
 };
 
 __device__ __forceinline__ double bperm_f64(double v, int src_lane) {
@@ -873,6 +880,11 @@ __device__ __forceinline__ double bperm_f64(double v, int src_lane) {
     const int lo = __builtin_amdgcn_ds_bpermute(src_lane << 2, (int)b);
     const int hi = __builtin_amdgcn_ds_bpermute(src_lane << 2, (int)(b >> 32));
     return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+
+__device__ __forceinline__ uint2 bperm_u2(const uint2 &v, int src_lane) {
+    return make_uint2((unsigned)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v.x),
+                      (unsigned)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v.y));
 }
 
 __device__ __forceinline__ void s1_edges_rows_wave(const BtArgs &a, int s, int nr,
@@ -883,6 +895,9 @@ __device__ __forceinline__ void s1_edges_rows_wave(const BtArgs &a, int s, int n
     const long long tb = (long long)s * a.CAP, db = (long long)s * a.MAXD;
     const long long SC = (long long)a.S * a.CAP;
     const double thresh = a.match_thresh;
+    constexpr unsigned WQ_POS_MASK = (1u << WQ_POS_BITS) - 1u;
+    const double psc = grid_pack_scale(h);   // the scale grid_build packed gv.pk with
+    const int nc = gv.sn;
     int m = 0;
     for (int base = t - lane; base < nr; base += nt, ++m) {   // wave-uniform loop
         const int i = base + lane;
@@ -891,6 +906,9 @@ __device__ __forceinline__ void s1_edges_rows_wave(const BtArgs &a, int s, int n
         if (on) rb = a.pool_box[tb + i];
         int cx0 = 0, cx1 = -1, cy0 = 0, cy1 = -1;
         if (!on || !grid_scan_window(h, rb, cx0, cx1, cy0, cy1)) cy1 = cy0 - 1;
+        // the row box as pass 1 compares it: packed like the grid's boxes (a coordinate outside the
+        // stream's range, infinities included, saturates outward)
+        const uint2 rp = box_pack16(rb, h.ox, h.oy, psc);
         // this row's candidate count (cells of a grid row are contiguous)
         int cnt = 0;
         for (int cy = cy0; cy <= cy1; ++cy)
@@ -899,7 +917,7 @@ __device__ __forceinline__ void s1_edges_rows_wave(const BtArgs &a, int s, int n
         const int off = incl - cnt;
         const int total = __builtin_amdgcn_readlane(incl, WAVE - 1);
         wq.cnt[lane] = 0;
-        wq.first[lane] = -1;
+        wq.first[lane] = 0xFFFF;
         for (int lo = 0; lo < total; lo += WQ_CAP) {
             const int hi = lo + WQ_CAP;
             // list this row's candidates whose wave index falls in [lo, hi)
@@ -909,40 +927,37 @@ __device__ __forceinline__ void s1_edges_rows_wave(const BtArgs &a, int s, int n
                     const int b = gv.cell_start[cy * h.gx + cx0], e = gv.cell_start[cy * h.gx + cx1 + 1];
                     const int k0 = idx < lo ? lo - idx : 0;
                     const int k1 = idx + (e - b) < hi ? e - b : hi - idx;
-                    for (int k = k0; k < k1; ++k) wq.q[idx + k - lo] = ((unsigned)lane << 24) | (unsigned)(b + k);
+                    for (int k = k0; k < k1; ++k)
+                        wq.q[idx + k - lo] = (unsigned short)((lane << WQ_POS_BITS) | (b + k));
                     idx += e - b;
                 }
             }
             __builtin_amdgcn_wave_barrier();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             const int n = total - lo < WQ_CAP ? total - lo : WQ_CAP;
-            // pass 1: keep the intersecting candidates (compacted in place: a survivor's new index
-            // is at most its old one, and a chunk is read before any of it is overwritten)
+            // pass 1: keep the candidates whose packed boxes meet (box16_meet: every pair that
+            // intersects in float64, and the few that rounding to 16 bits cannot tell apart),
+            // compacted in place: a survivor's new index is at most its old one, and a chunk is
+            // read before any of it is overwritten
             int ns = 0;
             // Two chunks of 64 per trip, every load of both issued before any test, and the test
-            // branch-free: a queued row box has x2 > x1 and y2 > y1 (grid_scan_window lists
-            // nothing otherwise, NaN included) and a binned box is usable, so intersects()
-            // reduces to its four cross comparisons - the same predicate on every queued pair.
-            // (The short-circuit form compiled to a chain of exec-masked LDS round trips.)
+            // branch-free: two dwords per row box through ds_bpermute, 8 B per candidate.
+            // (The short-circuit form compiled to a chain of exec-masked LDS round trips; the
+            // float64 form of this pass, 8 permutes and 32 B per candidate, is in commit 976ee6a.)
             const unsigned long long lt = (1ull << lane) - 1ull;
             for (int k0 = 0; k0 < n; k0 += 2 * WAVE) {   // wave-uniform trip count
                 const int ka = k0 + lane, kb = ka + WAVE;
                 const unsigned ea = wq.q[ka < n ? ka : 0], eb = wq.q[kb < n ? kb : 0];
-                const int ra = (int)(ea >> 24), pa = (int)(ea & 0xFFFFFFu);
-                const int rb_ = (int)(eb >> 24), pb = (int)(eb & 0xFFFFFFu);
-                const Box A{bperm_f64(rb.x1, ra), bperm_f64(rb.y1, ra), bperm_f64(rb.x2, ra),
-                            bperm_f64(rb.y2, ra)};
-                const Box B{bperm_f64(rb.x1, rb_), bperm_f64(rb.y1, rb_), bperm_f64(rb.x2, rb_),
-                            bperm_f64(rb.y2, rb_)};
-                const Box ca = s1_box(gv, pa), cb = s1_box(gv, pb);
-                const bool ha = (ka < n) & (A.x2 > ca.x1) & (ca.x2 > A.x1) & (A.y2 > ca.y1) &
-                                (ca.y2 > A.y1);
-                const bool hb = (kb < n) & (B.x2 > cb.x1) & (cb.x2 > B.x1) & (B.y2 > cb.y1) &
-                                (cb.y2 > B.y1);
+                const int ra = (int)(ea >> WQ_POS_BITS), pa = (int)(ea & WQ_POS_MASK);
+                const int rb_ = (int)(eb >> WQ_POS_BITS), pb = (int)(eb & WQ_POS_MASK);
+                const uint2 A = bperm_u2(rp, ra), B = bperm_u2(rp, rb_);
+                const uint2 ca = gv.pk[pa], cb = gv.pk[pb];
+                const bool ha = (ka < n) & box16_meet(A, ca);
+                const bool hb = (kb < n) & box16_meet(B, cb);
                 const unsigned long long ba = __ballot(ha), bb = __ballot(hb);
                 const int na = __popcll(ba);
-                if (ha) wq.q[ns + __popcll(ba & lt)] = ea;
-                if (hb) wq.q[ns + na + __popcll(bb & lt)] = eb;
+                if (ha) wq.q[ns + __popcll(ba & lt)] = (unsigned short)ea;
+                if (hb) wq.q[ns + na + __popcll(bb & lt)] = (unsigned short)eb;
                 ns += na + __popcll(bb);
             }
             __builtin_amdgcn_wave_barrier();
@@ -952,13 +967,19 @@ __device__ __forceinline__ void s1_edges_rows_wave(const BtArgs &a, int s, int n
                 const int k = k0 + lane;
                 // every operand's load issued before the row box arrives and before any branch
                 const unsigned ent = wq.q[k < ns ? k : 0];
-                const int r = (int)(ent >> 24), pos = (int)(ent & 0xFFFFFFu);
+                const int r = (int)(ent >> WQ_POS_BITS), pos = (int)(ent & WQ_POS_MASK);
                 const Box cb = s1_box(gv, pos);
                 const double wj = gv.w[pos];
-                const int j = gv.ids[pos];
+                const int j = gv.ids16[pos];
                 const Box tb_{bperm_f64(rb.x1, r), bperm_f64(rb.y1, r), bperm_f64(rb.x2, r),
                               bperm_f64(rb.y2, r)};
                 if (k >= ns) continue;
+                // The exact test pass 1 stood for: a queued row box has x2 > x1 and y2 > y1
+                // (grid_scan_window lists nothing otherwise, NaN included) and a binned box is
+                // usable, so intersects() reduces to its four cross comparisons.  The scored
+                // pairs are those of the float64 pass 1, whatever the packed test let through.
+                if (!((tb_.x2 > cb.x1) & (cb.x2 > tb_.x1) & (tb_.y2 > cb.y1) & (cb.y2 > tb_.y1)))
+                    continue;
                 const double dist = 1 - iou(tb_, cb);                   // matching.py:117
                 const double cost = 1 - (1 - dist) * wj;                // matching.py:216-220
                 if (!(cost < thresh)) continue;
@@ -967,7 +988,7 @@ __device__ __forceinline__ void s1_edges_rows_wave(const BtArgs &a, int s, int n
                     a.e_col[c * SC + tb + base + r] = j;
                     a.e_cost[c * SC + tb + base + r] = cost;
                 }
-                if (c == 0) wq.first[r] = j;
+                if (c == 0) wq.first[r] = (unsigned short)j;
                 atomicAdd(cdeg + j, 1);
             }
             __builtin_amdgcn_wave_barrier();
@@ -978,7 +999,7 @@ __device__ __forceinline__ void s1_edges_rows_wave(const BtArgs &a, int s, int n
         // big items: every query visits them (grid_query), boxes from the high lists
         if (on)
             for (int k = 0; k < h.n_big; ++k) {
-                const int j = gv.big[k];
+                const int j = gv.ids16[nc - 1 - k];
                 const Box cb = a.high_box[db + j];
                 if (!intersects(rb, cb)) continue;
                 const double dist = 1 - iou(rb, cb);
@@ -1100,7 +1121,8 @@ __global__ __launch_bounds__(NT, NT == BLKE ? 4 : 1) void k_s1_edges(BtArgs a) {
     // grid's build): these are this block's own stores, and every such read
     // follows a block_sync (the HBM path's own, grid_build's on the LDS path).
     int rn[4] = {0, 0, 0, 0}, rc[4] = {-1, -1, -1, -1};   // rows t + b * nt (s1_single_edges)
-    if (nc > 2 * nt || s1_grid_bytes(nc) + 4LL * nc > (long long)a.lds_bytes_e) {   // HBM grid
+    if (nc > 2 * nt || nc > (1 << WQ_POS_BITS) ||
+        s1_grid_bytes(nc) + 4LL * nc > (long long)a.lds_bytes_e) {   // HBM grid
         int *cdeg = a.g_deg + db;
         for (int j = t; j < nc; j += nt) cdeg[j] = 0;
         block_sync();
@@ -1119,12 +1141,14 @@ __global__ __launch_bounds__(NT, NT == BLKE ? 4 : 1) void k_s1_edges(BtArgs a) {
     GridView gv;
     gv.hdr = nullptr;
     gv.cell_start = ar.alloc<int>(grid_cells_for(nc) + 1);
-    gv.ids = ar.alloc<int>(nc);
+    gv.ids = nullptr;     // 16-bit ids, the big list at their array's end (nc <= 2 blockDim)
+    gv.big = nullptr;
+    gv.ids16 = ar.alloc<unsigned short>(nc);
     gv.boxes = nullptr;   // the boxes as four arrays (GridView::sx): conflict-free wave reads
     gv.sx = ar.alloc<double>(4LL * nc);
     gv.sn = nc;
     gv.w = ar.alloc<double>(nc);
-    gv.big = ar.alloc<int>(nc);
+    gv.pk = ar.alloc<uint2>(nc);   // and packed to 8 B for pass 1 of the row phase
     int *cdeg = ar.alloc<int>(nc);
     for (int j = t; j < nc; j += nt) cdeg[j] = 0;   // grid_build's barriers order these
     grid_build(nc, hbox, hw, gv, gs, wsum);
@@ -1142,11 +1166,11 @@ __global__ __launch_bounds__(NT, NT == BLKE ? 4 : 1) void k_s1_edges(BtArgs a) {
     if (t == 0) *gg.hdr = h;
     for (int q = t; q <= ncell; q += nt) gg.cell_start[q] = gv.cell_start[q];
     for (int q = t; q < h.n_binned; q += nt) {
-        gg.ids[q] = gv.ids[q];
+        gg.ids[q] = gv.ids16[q];
         gg.boxes[q] = s1_box(gv, q);
         gg.w[q] = gv.w[q];
     }
-    for (int q = t; q < h.n_big; q += nt) gg.big[q] = gv.big[q];
+    for (int q = t; q < h.n_big; q += nt) gg.big[q] = gv.ids16[nc - 1 - q];
 }
 
 // Arena bytes that always suffice for s1_lap_body (the global fallback arena's size): compact
@@ -2993,7 +3017,7 @@ constexpr size_t BT_LDSF_BYTES = YTA_LDSF_KB * 1024;   // k_finish dedup arena (
 #endif
 constexpr size_t BT_LDSL_BYTES = YTA_LDSL_KB * 1024;   // k_s1_lap arena (four blocks per CU)
 #ifndef YTA_LDSE_KB
-#define YTA_LDSE_KB 62
+#define YTA_LDSE_KB 63
 #endif
 constexpr size_t BT_LDSE_BYTES = YTA_LDSE_KB * 1024;   // k_s1_edges grid (1024 high detections)
 

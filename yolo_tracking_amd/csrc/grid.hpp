@@ -46,7 +46,60 @@ struct GridView {
     // (no LDS bank conflicts), where 32-B records put two lanes on every bank pair it touches
     double *sx = nullptr;         // 4 arrays of n doubles: sx, sx + n, sx + 2 n, sx + 3 n
     int sn = 0;
+    // 16-bit ids instead of `ids` and `big` (n <= 65536): the binned ids in cell order from the
+    // front, the big list from the back (big item k at ids16[sn - 1 - k]; n_binned + n_big <= sn)
+    unsigned short *ids16 = nullptr;
+    // the binned boxes once more as 16-bit fixed point (box_pack16), cell order: the conservative
+    // pre-test of k_s1_edges reads 8 B per candidate
+    uint2 *pk = nullptr;
 };
+
+// ---- 16-bit fixed-point boxes: a conservative intersection pre-test (k_s1_edges)
+// A coordinate x maps through f(x) = (x - origin) * scale, clamped to [0, 65535]; lower corners
+// are rounded down, upper corners up.  The float64 subtraction and the multiplication by a scale
+// >= 0 are monotone, and so are floor, ceil and the clamp, hence a > b implies
+// pack16_up(a) >= pack16_dn(b): two boxes that intersect in float64 pass box16_meet, whatever the
+// origin and the scale are.  A NaN (a NaN coordinate, or inf * 0 with a zero scale) goes to the
+// far end of its side (0 down, 65535 up), which passes every comparison it takes part in.
+__host__ __device__ __forceinline__ unsigned pack16_dn(double x, double o, double sc) {
+    const double v = floor((x - o) * sc);
+    return v >= 0.0 ? (v < 65535.0 ? (unsigned)v : 65535u) : 0u;
+}
+__host__ __device__ __forceinline__ unsigned pack16_up(double x, double o, double sc) {
+    const double v = ceil((x - o) * sc);
+    return v <= 65535.0 ? (v > 0.0 ? (unsigned)v : 0u) : 65535u;
+}
+// .x = x1 | y1 << 16 (rounded down), .y = x2 | y2 << 16 (rounded up)
+__host__ __device__ __forceinline__ uint2 box_pack16(const Box &b, double ox, double oy,
+                                                     double sc) {
+    uint2 p;
+    p.x = pack16_dn(b.x1, ox, sc) | (pack16_dn(b.y1, oy, sc) << 16);
+    p.y = pack16_up(b.x2, ox, sc) | (pack16_up(b.y2, oy, sc) << 16);
+    return p;
+}
+// One scale for both axes, from the header alone: the top-left corners span less than gx * g by
+// gy * g (grid_build: gx = floor(extent / g) + 1), so every binned box ends within
+// r = gx * g + maxw of the origin, up to a few roundings (1e-15 relative).  Mapping r to 65534
+// leaves a margin of 1.5e-5 for those: no binned box saturates, its packed box contains it (the
+// intersection test does not need that: saturation is conservative there).
+// 0 (every box packs to zeros: all pairs pass) without a finite positive range.
+__host__ __device__ __forceinline__ double grid_pack_scale(const GridHdr &h) {
+    const double rx = (double)h.gx * h.g + h.maxw, ry = (double)h.gy * h.g + h.maxh;
+    const double r = rx > ry ? rx : ry;
+    return r > 0.0 && r < INFINITY ? 65534.0 / r : 0.0;
+}
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+// both 16-bit halves of u >= those of v (v_pk_max_u16 + one compare)
+__host__ __device__ __forceinline__ bool pk16_ge(unsigned u, unsigned v) {
+    const u16x2 m = __builtin_elementwise_max(__builtin_bit_cast(u16x2, u),
+                                              __builtin_bit_cast(u16x2, v));
+    return __builtin_bit_cast(unsigned, m) == u;
+}
+// false only when the float64 boxes behind a and b (packed with one origin and scale) do not
+// intersect: the four cross comparisons with >=, since rounding can close a gap but not open one
+__host__ __device__ __forceinline__ bool box16_meet(const uint2 &a, const uint2 &b) {
+    return (int)pk16_ge(a.y, b.x) & (int)pk16_ge(b.y, a.x);   // branch-free
+}
 
 // Box of the binned item at cell-order position k.
 __device__ __forceinline__ Box grid_box(const GridView &gv, int k) {
@@ -59,6 +112,45 @@ __host__ __device__ __forceinline__ bool box_usable(const Box &b) {
     const double w = b.x2 - b.x1, h = b.y2 - b.y1;
     return w > 0.0 && h > 0.0 && isfinite(b.x1) && isfinite(b.y1) && isfinite(b.x2) &&
            isfinite(b.y2) && isfinite(w) && isfinite(h);
+}
+
+// The grid's geometry from the reduction over the usable boxes, v = {sum of max(w, h), count,
+// min x1, min y1, max x1, max y1}: the mean size, which boxes are binned (the others are "big"),
+// and origin / cell size / cell counts for n items (n_big, n_binned, maxw, maxh come later).
+// Host-callable so that the packed pre-test can be evaluated without a GPU (yta_s1_pretest).
+__host__ __device__ __forceinline__ double grid_mean_size(const double v[6]) {
+    return v[1] > 0 ? v[0] / v[1] : 1.0;
+}
+__host__ __device__ __forceinline__ bool grid_binned(const Box &b, double bthr) {
+    return box_usable(b) && !(b.x2 - b.x1 > bthr) && !(b.y2 - b.y1 > bthr);
+}
+__host__ __device__ __forceinline__ GridHdr grid_geometry(const double v[6], int n) {
+    GridHdr h;
+    h.maxw = h.maxh = 0.0;
+    h.n_big = h.n_binned = 0;
+    if (!(v[4] >= v[2])) {   // nothing usable
+        h.ox = h.oy = 0.0;
+        h.g = 1.0;
+        h.inv_g = 1.0;
+        h.gx = h.gy = 1;
+        return h;
+    }
+    double g = grid_mean_size(v);
+    const double ex = v[4] - v[2], ey = v[5] - v[3];
+    double gxf = floor(ex / g) + 1.0, gyf = floor(ey / g) + 1.0;
+    const double max_cells = (double)grid_cells_for(n);
+    while (gxf * gyf > max_cells) {
+        g *= 1.25;
+        gxf = floor(ex / g) + 1.0;
+        gyf = floor(ey / g) + 1.0;
+    }
+    h.ox = v[2];
+    h.oy = v[3];
+    h.g = g;
+    h.inv_g = 1.0 / g;
+    h.gx = (int)gxf;
+    h.gy = (int)gyf;
+    return h;
 }
 
 __device__ __forceinline__ int grid_cell_1d(double x, double o, double inv_g, int n) {
@@ -88,7 +180,8 @@ __device__ __forceinline__ void block_reduce6(double v[6], const int op[6], doub
 
 // Block-wide build (every thread of the block calls it).  box(i) returns item i's box, wof(i) its
 // weight (stored only when gv.w is set).  gv.cell_start needs grid_cells_for(n) + 1 entries,
-// gv.ids / gv.boxes / gv.w / gv.big n entries.
+// gv.ids / gv.boxes / gv.w / gv.big n entries (gv.ids16 with gv.sn = n replaces ids and big;
+// gv.pk, n entries, is optional).
 //   1. one block reduction over the usable boxes: mean size, extent of the top-left corners
 //   2. count per cell (items larger than 4 x mean go to the big list instead); the maximum
 //      width / height of the binned items by 64-bit LDS atomicMax on their bit patterns
@@ -117,34 +210,9 @@ __device__ __forceinline__ void grid_build(int n, BoxOf box, WOf wof, GridView g
     }
     block_reduce6(v, ops, gs.red);
     YTA_STAMP_ABS(111);
-    const double mean = v[1] > 0 ? v[0] / v[1] : 1.0;
-    const double bthr = 4.0 * mean;
-    auto binned = [&](const Box &b) {
-        return box_usable(b) && !(b.x2 - b.x1 > bthr) && !(b.y2 - b.y1 > bthr);
-    };
-    GridHdr h;
-    if (!(v[4] >= v[2])) {   // nothing usable
-        h.ox = h.oy = 0.0;
-        h.g = 1.0;
-        h.inv_g = 1.0;
-        h.gx = h.gy = 1;
-    } else {
-        double g = mean;
-        const double ex = v[4] - v[2], ey = v[5] - v[3];
-        double gxf = floor(ex / g) + 1.0, gyf = floor(ey / g) + 1.0;
-        const double max_cells = (double)grid_cells_for(n);
-        while (gxf * gyf > max_cells) {
-            g *= 1.25;
-            gxf = floor(ex / g) + 1.0;
-            gyf = floor(ey / g) + 1.0;
-        }
-        h.ox = v[2];
-        h.oy = v[3];
-        h.g = g;
-        h.inv_g = 1.0 / g;
-        h.gx = (int)gxf;
-        h.gy = (int)gyf;
-    }
+    const double bthr = 4.0 * grid_mean_size(v);
+    auto binned = [&](const Box &b) { return grid_binned(b, bthr); };
+    GridHdr h = grid_geometry(v, n);
     const int ncell = h.gx * h.gy;
     int *cs = gv.cell_start;
     for (int c = t; c <= ncell; c += nt) cs[c] = 0;
@@ -160,7 +228,9 @@ __device__ __forceinline__ void grid_build(int n, BoxOf box, WOf wof, GridView g
         const Box b = box(i);
         if (!box_usable(b)) continue;
         if (!binned(b)) {
-            gv.big[atomicAdd(&gs.hdr.n_big, 1)] = i;
+            const int k = atomicAdd(&gs.hdr.n_big, 1);
+            if (gv.ids16) gv.ids16[gv.sn - 1 - k] = (unsigned short)i;
+            else gv.big[k] = i;
             continue;
         }
         mw = fmax(mw, b.x2 - b.x1);
@@ -198,12 +268,15 @@ __device__ __forceinline__ void grid_build(int n, BoxOf box, WOf wof, GridView g
     }
     block_sync();
     YTA_STAMP_ABS(115);
+    const double psc = gv.pk ? grid_pack_scale(gs.hdr) : 0.0;   // maxw / maxh are known by now
     for (int i = t; i < n; i += nt) {
         const Box b = box(i);
         if (!binned(b)) continue;
         const int pos = atomicAdd(&cs[cell_of(b) + 1], 1);
-        gv.ids[pos] = i;
+        if (gv.ids16) gv.ids16[pos] = (unsigned short)i;
+        else gv.ids[pos] = i;
         if (gv.boxes) gv.boxes[pos] = b;
+        if (gv.pk) gv.pk[pos] = box_pack16(b, h.ox, h.oy, psc);
         if (gv.sx) {
             gv.sx[pos] = b.x1;
             gv.sx[gv.sn + pos] = b.y1;
