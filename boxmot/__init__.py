@@ -22,20 +22,11 @@ import types
 
 import yolo_tracking_amd as _yta
 from yolo_tracking_amd import (TRACKERS, BoTSORT, BYTETracker, DeepOCSort, HybridSORT,  # noqa: F401
-                               OCSort, __version__, create_tracker, get_tracker_config, gsi)
+                               OCSort, StrongSORT, __version__, create_tracker,
+                               get_tracker_config, gsi)
 
 OCSORT = OCSort          # boxmot/__init__.py:7 exports the OCSort class under this name
 DeepOCSORT = DeepOCSort  # boxmot/__init__.py:8
-
-
-class _StrongSORT:
-    """boxmot/__init__.py:10: StrongSORT is outside the MI355X path."""
-
-    def __init__(self, *a, **k):
-        raise NotImplementedError("StrongSORT is not on the MI355X path; see DESIGN.md §7")
-
-
-StrongSORT = _StrongSORT
 
 # reference module path -> module of this build (boxmot/ tree of the reference, v10.0.51)
 ALIASES = {
@@ -49,6 +40,7 @@ ALIASES = {
     "boxmot.trackers.ocsort.ocsort": "yolo_tracking_amd.trackers.ocsort",
     "boxmot.trackers.deepocsort.deep_ocsort": "yolo_tracking_amd.trackers.deepocsort",
     "boxmot.trackers.hybridsort.hybridsort": "yolo_tracking_amd.trackers.hybridsort",
+    "boxmot.trackers.strongsort.strong_sort": "yolo_tracking_amd.trackers.strongsort",
     "boxmot.postprocessing": "yolo_tracking_amd.postprocessing",
     "boxmot.postprocessing.gsi": "yolo_tracking_amd.postprocessing.gsi",
     "boxmot.appearance": "yolo_tracking_amd.appearance",

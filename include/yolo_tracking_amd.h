@@ -44,6 +44,15 @@
  *                            BGR -> RGB, ImageNet standardisation, NCHW batch)
  *   yta_reid_normalize*      boxmot/appearance/reid_multibackend.py:303-311 get_features'
  *                            `features / np.linalg.norm(features)`
+ *   yta_strongsort_*         boxmot/trackers/strongsort/strong_sort.py:13-99 StrongSORT
+ *                            (sort/tracker.py, sort/track.py, sort/linear_assignment.py,
+ *                            sort/iou_matching.py, motion/kalman_filters/strongsort_kf.py,
+ *                            utils/matching.py:224-378); ReID and ECC outside
+ *   yta_lsa_replay           scipy.optimize.linear_sum_assignment as called by
+ *                            strongsort/sort/linear_assignment.py:61
+ *   yta_nn_cosine_min        boxmot/utils/matching.py:247-308 _nn_cosine_distance
+ *   yta_kf_nsa_update        boxmot/motion/kalman_filters/strongsort_kf.py:124-189
+ *   yta_kf_xyah_gating       boxmot/motion/kalman_filters/strongsort_kf.py:191-233
  */
 #ifndef YOLO_TRACKING_AMD_H
 #define YOLO_TRACKING_AMD_H
@@ -740,6 +749,84 @@ int yta_reid_preprocess_tensors(const void *const *d_frames, const int *d_img_hw
 int yta_reid_normalize(int device, float *feats, long long count);
 /* Device form: d_work holds >= 256 doubles of scratch. */
 int yta_reid_normalize_device(float *d_feats, long long count, double *d_work, void *stream);
+
+/* ---- StrongSORT (boxmot/trackers/strongsort/strong_sort.py:13-99) ---------------------------
+ * S streams per engine.  Per frame and stream: camera_update of every track by the 2x3 warp
+ * (sort/track.py:129-138), predict (strongsort_kf.py:87-122), the matching cascade of the confirmed
+ * tracks on min-over-gallery cosine distance (utils/matching.py:290-308, :360-378) gated by the
+ * Mahalanobis distance (sort/linear_assignment.py:144-200), IoU matching of the rest
+ * (sort/iou_matching.py:10-87, sort/tracker.py:139-153), both solved by a replay of
+ * scipy.optimize.linear_sum_assignment (sort/linear_assignment.py:59-78: its tie-breaking decides
+ * the order of the births, hence the ids), the NSA update (strongsort_kf.py:124-189), the EMA
+ * feature (sort/track.py:168-174), births / deletions (sort/tracker.py:88-94) and the gallery
+ * (sort/tracker.py:96-106, utils/matching.py:343-358).  The ReID features and the ECC warp
+ * (strong_sort.py:63, :68) are inputs.  The float32 products and norms, whose order the reference
+ * leaves to BLAS, have the fixed order stated in csrc/strongsort.hip. */
+typedef struct yta_strongsort yta_strongsort;
+typedef struct {
+    double max_dist;       /* strongsort.yaml / strong_sort.py:19   0.2   */
+    double max_iou_dist;   /* strong_sort.py:20                      0.7   */
+    int max_age;           /* strong_sort.py:21                      30    */
+    int n_init;            /* strong_sort.py:22                      1     */
+    double mc_lambda;      /* strong_sort.py:24                      0.995 */
+    double ema_alpha;      /* strong_sort.py:25                      0.9   */
+} yta_strongsort_params;
+/* nn_budget (strong_sort.py:23, utils/matching.py:356-357): gallery rows kept per track.  The
+ * galleries take n_streams x track_capacity x nn_budget x feat_dim x 4 B; a size above the
+ * device's free memory returns YTA_ERR_NOMEM with the figures in yta_last_error() and allocates
+ * nothing.  track_capacity and max_dets are limited to 3072. */
+int yta_strongsort_create(int device, int n_streams, int track_capacity, int max_dets,
+                          int feat_dim, int nn_budget, const yta_strongsort_params *params,
+                          yta_strongsort **engine);
+int yta_strongsort_destroy(yta_strongsort *engine);
+/* Empty track lists, id counters back to 1 (sort/tracker.py:58-59). */
+int yta_strongsort_reset(yta_strongsort *engine);
+int yta_strongsort_capacity(yta_strongsort *engine, int *track_capacity, int *max_dets,
+                            int *feat_dim, int *nn_budget);
+/* Host-buffer update (synchronous), strong_sort.py:42-99.  dets: rows x1 y1 x2 y2 conf cls of all
+ * streams, stream s = rows det_offsets[s] .. det_offsets[s + 1]; feats: feat_dim float32 per row
+ * (what get_features returns, strong_sort.py:68); warps: S x 6 float64 row-major 2x3 or NULL, a row
+ * whose first value is NaN = no camera update for that stream (strong_sort.py:62: the estimator
+ * runs only while the tracker holds a track); out: rows x1 y1 x2 y2 id conf cls det_ind
+ * (strong_sort.py:83-96), stream s = rows out_offsets[s] .. out_offsets[s + 1]; n_tracks (S, may be
+ * NULL): tracks held after the frame, tentative ones included.  YTA_ERR_CAPACITY when a stream
+ * needs more than track_capacity tracks; the engine must then be reset. */
+int yta_strongsort_update(yta_strongsort *engine, const double *dets, const int *det_offsets,
+                          const float *feats, const double *warps, double *out, int out_capacity,
+                          int *out_offsets, int *n_tracks);
+/* Device-resident update (asynchronous on the engine's stream).  d_dets: S x max_dets x 6,
+ * d_det_counts: S, d_feats: S x max_dets x feat_dim, d_warps: S x 6 or NULL, d_out: S x
+ * track_capacity x 8, d_out_counts: S, d_n_tracks: S or NULL.  yta_strongsort_sync waits and
+ * reports a capacity error. */
+int yta_strongsort_update_device(yta_strongsort *engine, const double *d_dets,
+                                 const int *d_det_counts, const float *d_feats,
+                                 const double *d_warps, double *d_out, int *d_out_counts,
+                                 int *d_n_tracks);
+int yta_strongsort_sync(yta_strongsort *engine);
+/* Tracks of one stream in list order (parity introspection); every pointer but n_tracks may be
+ * NULL.  ints: n x 5 (id, hits, age, time_since_update, state 1 tentative / 2 confirmed); mean
+ * n x 8; cov n x 64; feat n x feat_dim (features[-1]); gallery_len n; gallery n x nn_budget x
+ * feat_dim, rows g / |g| in ring order. */
+int yta_strongsort_get_state(yta_strongsort *engine, int stream, int *n_tracks, long long *ints,
+                             double *mean, double *cov, float *feat, int *gallery_len,
+                             float *gallery);
+int yta_strongsort_hip_stream(yta_strongsort *engine, void **stream);
+/* scipy.optimize.linear_sum_assignment(cost) (sort/linear_assignment.py:61) replayed on the
+ * device, ties included: min(nr, nc) pairs sorted by row. */
+int yta_lsa_replay(int device, int nr, int nc, const double *cost, int *rows, int *cols);
+/* _nn_cosine_distance (utils/matching.py:247-308) per track: gallery n_tracks x budget x feat_dim
+ * raw rows, lens[t] (1..budget) valid rows; feats n_dets x feat_dim raw; out n_tracks x n_dets
+ * float32 = min over the rows of 1 - <g / |g|, f / |f|> in the engine's float32 order. */
+int yta_nn_cosine_min(int device, int n_tracks, int budget, int feat_dim, const float *gallery,
+                      const int *lens, int n_dets, const float *feats, float *out);
+/* strongsort_kf.py:124-189 update(mean, covariance, measurement, confidence) of n tracks in place
+ * (mean n x 8, cov n x 64 full, z n x 4, conf n). */
+int yta_kf_nsa_update(int device, int n, double *mean, double *cov, const double *z,
+                      const double *conf);
+/* strongsort_kf.py:191-233 gating_distance(mean, covariance, measurements) of n tracks against m
+ * measurements (zs m x 4) -> out n x m. */
+int yta_kf_xyah_gating(int device, int n, const double *mean, const double *cov, int m,
+                       const double *zs, double *out);
 
 /* ---- Camera-motion compensation: SparseOptFlow (boxmot/motion/cmc/sof.py:15-162) -------------
  * The estimator BoTSORT (bot_sort.py:228, :293) and DeepOCSort (deep_ocsort.py:351, :391) call once

@@ -6,12 +6,18 @@
     python tools/bench_tracker.py --tracker deepocsort [--n 2048] [--dim 512] [--streams 1]
     python tools/bench_tracker.py --tracker hybridsort [--n 4096] [--dim 512] [--streams 8]
     python tools/bench_tracker.py --tracker ocsort --tensors [--repeats 3] [--out FILE.jsonl]
+    python tools/bench_tracker.py --tracker strongsort [--n 1024] [--dim 512] [--budget 100]
+                                  [--warmup 100] [--out FILE.jsonl]
 
 A step = one update() frame of every stream (SURVEY.md §8(d) synthetic streams; OCSORT with
 ocsort.yaml parameters and no low-confidence detections, BoT-SORT with botsort.yaml parameters
 and D-dim float32 embeddings through the get_features convention), inputs staged in HBM, the
 engine's device-buffer entry point, K timed frames bracketed by device syncs.  The CPU baseline
 is the oracle restatement of the same tracker on one core over a bounded sample of the stream.
+StrongSORT (run_strongsort): strongsort.yaml parameters, every detection with a D-dim feature row,
+galleries of --budget rows (full after --warmup >= budget frames), the engine's device-buffer
+entry point; the CPU leg is the NumPy restatement (tests/strongsort_oracle.py, its gallery product
+through sgemm) on one core.
 bench.py (the driver's contract) measures the ByteTrack headline; this tool is for DESIGN.md.
 """
 import argparse
@@ -35,10 +41,13 @@ BOTSORT_YAML = dict(track_high_thresh=0.33824964456239337, track_low_thresh=0.1,
                     appearance_thresh=0.4818211117541298, frame_rate=30)
 DEEPOCSORT_YAML = dict(det_thresh=0.0, max_age=30, min_hits=1, iou_threshold=0.3, delta_t=3,
                        asso_func="giou", inertia=0.2)          # create_tracker's arguments
+STRONGSORT_YAML = dict(max_dist=0.2, max_iou_dist=0.7, max_age=30, n_init=1, mc_lambda=0.995,
+                       ema_alpha=0.8)                          # boxmot/configs/strongsort.yaml
 HYBRIDSORT_YAML = dict(det_thresh=0.0, max_age=30, min_hits=1, iou_threshold=0.3, delta_t=3,
                        asso_func="giou", inertia=0.2)
 CMC_AFFINE = [[1.0, 1e-3, 0.5], [-1e-3, 1.0, -0.3]]
-DEFAULT_N = {"ocsort": 256, "botsort": 1024, "deepocsort": 2048, "hybridsort": 4096}
+DEFAULT_N = {"ocsort": 256, "botsort": 1024, "deepocsort": 2048, "hybridsort": 4096,
+             "strongsort": 1024}
 
 
 def reid_rows(dets, embs, thr):
@@ -58,8 +67,9 @@ def cpu_leg(code, timeout=900):
 
 def parse(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument("--tracker", choices=["ocsort", "botsort", "deepocsort", "hybridsort"],
-                   required=True)
+    p.add_argument("--tracker", choices=["ocsort", "botsort", "deepocsort", "hybridsort",
+                                         "strongsort"], required=True)
+    p.add_argument("--budget", type=int, default=100, help="strongsort: nn_budget")
     p.add_argument("--n", type=int, default=None)
     p.add_argument("--dim", type=int, default=512)
     p.add_argument("--streams", type=int, default=1)
@@ -78,7 +88,8 @@ def parse(argv=None):
     p.add_argument("--repeats", type=int, default=3, help="--tensors: runs of each leg")
     p.add_argument("--cap-mult", type=int, default=2,
                    help="--tensors: track_capacity / n of both legs' engines (2: the configs')")
-    p.add_argument("--out", default=None, help="--tensors: also append the JSON lines here")
+    p.add_argument("--out", default=None,
+                   help="--tensors / strongsort: also append the JSON lines here")
     return p.parse_args(argv)
 
 
@@ -497,8 +508,93 @@ def run_tensors(args):
     return lines
 
 
+def run_strongsort(args):
+    """StrongSORT at N tracks x N detections, D-dim features, galleries of --budget rows: device
+    calls/s of yta_strongsort_update_device (inputs staged in HBM, K timed frames bracketed by
+    device syncs) beside the restatement on one core."""
+    import torch
+    from yolo_tracking_amd import StrongSortEngine, _lib
+    from yolo_tracking_amd.synth import make_frames
+    S, N, D, B = args.streams, args.n or DEFAULT_N["strongsort"], args.dim, args.budget
+    F = args.warmup + args.steps
+    seeds = [args.seed + s for s in range(S)]
+    streams = [make_frames(N, F, seeds[s], emb_dim=D, low_conf_frac=0.0) for s in range(S)]
+    eng = StrongSortEngine(S, feat_dim=D, nn_budget=B, track_capacity=2 * N, max_dets=N,
+                           **STRONGSORT_YAML)
+    cap, maxd = eng.capacity()
+    dets = np.zeros((F, S, maxd, 6))
+    feats = np.zeros((F, S, maxd, D), np.float32)
+    cnt = np.zeros((F, S), np.int32)
+    for s in range(S):
+        for f, (d, e) in enumerate(streams[s]):
+            cnt[f, s] = len(d)
+            dets[f, s, :len(d)] = d
+            feats[f, s, :len(d)] = e
+    d_dets, d_feats, d_cnt = (torch.from_numpy(x).cuda() for x in (dets, feats, cnt))
+    d_out = torch.empty((S * cap, 8), dtype=torch.float64, device="cuda")
+    d_nout = torch.zeros(S, dtype=torch.int32, device="cuda")
+    d_ntrk = torch.zeros(S, dtype=torch.int32, device="cuda")
+    fn, sync = eng.lib.yta_strongsort_update_device, eng.lib.yta_strongsort_sync
+    P = ctypes.c_void_p
+
+    def step(f):
+        _lib.check(fn(eng.handle, P(d_dets[f].data_ptr()), P(d_cnt[f].data_ptr()),
+                      P(d_feats[f].data_ptr()), None, P(d_out.data_ptr()), P(d_nout.data_ptr()),
+                      P(d_ntrk.data_ptr())))
+
+    torch.cuda.synchronize()
+    for f in range(args.warmup):
+        step(f)
+    _lib.check(sync(eng.handle))
+    t0 = time.perf_counter()
+    for f in range(args.warmup, F):
+        step(f)
+    _lib.check(sync(eng.handle))
+    el = time.perf_counter() - t0
+    st = eng.state(0)
+    conf = st["state"] == 2
+    cf = args.cpu_frames if args.cpu_frames is not None else 3
+    cpu = {"value": None, "sample": "skipped (--cpu-frames 0)"}
+    if cf:
+        code = ("import sys,time,json; sys.path.insert(0,%r); sys.path.insert(0,%r)\n"
+                "from strongsort_oracle import StrongSortOracle\n"
+                "from yolo_tracking_amd.synth import make_frames\n"
+                "fr=make_frames(%d,%d,%d,emb_dim=%d,low_conf_frac=0.0)\n"
+                "t=StrongSortOracle(nn_budget=%d,fast=True,**%r); t.update(*fr[0])\n"
+                "t0=time.perf_counter()\n"
+                "for d,e in fr[1:]: t.update(d,e)\n"
+                "print(json.dumps({'frames':len(fr)-1,'seconds':time.perf_counter()-t0}))\n"
+                % (REPO, os.path.join(REPO, "tests"), N, cf + 1, args.seed, D, B, STRONGSORT_YAML))
+        res = cpu_leg(code)
+        cpu = ({"value": res["frames"] / res["seconds"], "unit": "calls/s", "cores": 1,
+                "kind": "restatement",
+                "sample": f"tests/strongsort_oracle.py (sgemm gallery product) 1 stream {N}x{N}, "
+                          f"frames 2..{cf + 1} of seed {args.seed} (galleries <= {cf} rows), "
+                          f"{res['seconds']:.1f} s, 1 thread"}
+               if "frames" in res else {"value": None, "sample": res.get("error")})
+    line = {"metric": f"strongsort tracker.update() calls/sec @ {N} tracks x {N} dets",
+            "value": S * args.steps / el, "unit": "calls/s", "n_gpus": 1, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1000 * el / args.steps,
+            "higher_is_better": True, "dtype": "f64 state, f32 features", "data": "synthetic",
+            "config": {"workload": f"strongsort {N}x{N} D={D} nn_budget={B}, {S} streams, inputs "
+                                   "resident in HBM", "streams": S},
+            "cpu_baseline": cpu,
+            "frame_counts": {"tracks": int(len(conf)), "confirmed": int(conf.sum()),
+                             "gallery_rows_mean": float(st["gallery_len"][conf].mean())
+                             if conf.any() else 0.0,
+                             "out": int(d_nout.cpu()[0])},
+            "elapsed_s": el, "stream_seeds": seeds}
+    print(json.dumps(line))
+    if args.out:
+        with open(args.out, "a") as fh:
+            fh.write(json.dumps(line) + "\n")
+
+
 def main():
     args = parse()
+    if args.tracker == "strongsort":
+        run_strongsort(args)
+        return
     if args.tensors:
         run_tensors(args)
         return

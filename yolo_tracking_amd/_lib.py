@@ -87,6 +87,13 @@ class HsParams(ctypes.Structure):
                 ("inertia", ctypes.c_double)]
 
 
+class SsParams(ctypes.Structure):
+    """yta_strongsort_params (include/yolo_tracking_amd.h)."""
+    _fields_ = [("max_dist", ctypes.c_double), ("max_iou_dist", ctypes.c_double),
+                ("max_age", ctypes.c_int), ("n_init", ctypes.c_int),
+                ("mc_lambda", ctypes.c_double), ("ema_alpha", ctypes.c_double)]
+
+
 ASSO_FUNCS = {"iou": 0, "giou": 1, "diou": 2, "ciou": 3, "centroid": 4}
 
 _lib = None
@@ -209,6 +216,19 @@ _SIGS = {
     "yta_hybridsort_lap_stats": ([_P, _P, _I], _I),
     "yta_hybridsort_hip_stream": ([_P, _P], _I),
     "yta_kf9_run": ([_I, _I, _I, _P, _P, _P, _P], _I),
+    "yta_strongsort_create": ([_I, _I, _I, _I, _I, _I, _P, _P], _I),
+    "yta_strongsort_destroy": ([_P], _I),
+    "yta_strongsort_reset": ([_P], _I),
+    "yta_strongsort_capacity": ([_P, _P, _P, _P, _P], _I),
+    "yta_strongsort_update": ([_P, _P, _P, _P, _P, _P, _I, _P, _P], _I),
+    "yta_strongsort_update_device": ([_P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "yta_strongsort_sync": ([_P], _I),
+    "yta_strongsort_get_state": ([_P, _I, _P, _P, _P, _P, _P, _P, _P], _I),
+    "yta_strongsort_hip_stream": ([_P, _P], _I),
+    "yta_lsa_replay": ([_I, _I, _I, _P, _P, _P], _I),
+    "yta_nn_cosine_min": ([_I, _I, _I, _I, _P, _P, _I, _P, _P], _I),
+    "yta_kf_nsa_update": ([_I, _I, _P, _P, _P, _P], _I),
+    "yta_kf_xyah_gating": ([_I, _I, _P, _P, _I, _P, _P], _I),
     "yta_gsi_interpolate": ([_I, _P, _I, _I, _I, _I, _P, ctypes.c_longlong, _P], _I),
     "yta_gsi_smooth": ([_I, _P, _P, _P, _P, _P, _I, _P], _I),
     "yta_embedding_distance": ([_I, _P, _I, _P, _I, _I, _P], _I),
@@ -462,6 +482,51 @@ def affine_apply(kind, warps, mean, cov, device=0):
     assert len(w) == len(m) == len(c)
     check(load_library().yta_affine_apply(device, int(kind), len(m), ptr(w), ptr(m), ptr(c)))
     return m, c
+
+
+def lsa_replay(cost, device=0):
+    """scipy.optimize.linear_sum_assignment(cost) replayed on the device -> (rows, cols)."""
+    c = np.ascontiguousarray(cost, dtype=np.float64)
+    nr, nc = c.shape
+    k = min(nr, nc)
+    rows = np.empty(k, dtype=np.int32)
+    cols = np.empty(k, dtype=np.int32)
+    check(load_library().yta_lsa_replay(device, nr, nc, ptr(c), ptr(rows), ptr(cols)))
+    return rows, cols
+
+
+def nn_cosine_min(gallery, lens, feats, device=0):
+    """matching.py:290-308 per track: gallery (T, B, D) raw float32 rows, lens (T,) valid rows,
+    feats (M, D) raw -> (T, M) float32 in the StrongSORT engine's float32 order."""
+    g = np.ascontiguousarray(gallery, dtype=np.float32)
+    T, B, D = g.shape
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    f = np.ascontiguousarray(feats, dtype=np.float32).reshape(-1, D)
+    out = np.empty((T, len(f)), dtype=np.float32)
+    check(load_library().yta_nn_cosine_min(device, T, B, D, ptr(g), ptr(ln), len(f), ptr(f),
+                                           ptr(out)))
+    return out
+
+
+def kf_nsa_update(mean, cov, z, conf, device=0):
+    """strongsort_kf.py:124-189 update with a confidence per track."""
+    mean = np.array(mean, dtype=np.float64, order="C").reshape(-1, 8)
+    cov = np.array(cov, dtype=np.float64, order="C").reshape(-1, 8, 8)
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(-1, 4)
+    q = np.ascontiguousarray(np.broadcast_to(np.asarray(conf, dtype=np.float64), (len(mean),)))
+    check(load_library().yta_kf_nsa_update(device, len(mean), ptr(mean), ptr(cov), ptr(z), ptr(q)))
+    return mean, cov
+
+
+def kf_xyah_gating(mean, cov, zs, device=0):
+    """strongsort_kf.py:191-233 gating_distance of n tracks against m measurements -> (n, m)."""
+    mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1, 8)
+    cov = np.ascontiguousarray(cov, dtype=np.float64).reshape(-1, 8, 8)
+    zs = np.ascontiguousarray(zs, dtype=np.float64).reshape(-1, 4)
+    out = np.empty((len(mean), len(zs)))
+    check(load_library().yta_kf_xyah_gating(device, len(mean), ptr(mean), ptr(cov), len(zs),
+                                            ptr(zs), ptr(out)))
+    return out
 
 
 def lap_first_round(cost, device=0):

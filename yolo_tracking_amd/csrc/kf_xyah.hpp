@@ -135,6 +135,62 @@ __host__ __device__ inline void kf_update(KfState &s, const double *z) {
     }
 }
 
+// ---------------------------------------------------------------- StrongSORT (strongsort_kf.py)
+// initiate / predict are ByteTrack's (strongsort_kf.py:54-122, same stds).  project (:124-155)
+// scales the measurement std by (1 - confidence), the NSA Kalman filter; the projected covariance
+// stays diagonal, so cho_factor / cho_solve (:179-183) reduce to kf_update's per-axis form.
+__host__ __device__ __forceinline__ double kf_nsa_std(const double *m, int i, double conf) {
+    return (1 - conf) * (i == 2 ? 1e-1 : KF_W_POS * m[3]);
+}
+__host__ __device__ inline void kf_update_nsa(KfState &s, const double *z, double conf) {
+    double r[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = kf_nsa_std(s.m, i, conf);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double pp = s.c[4 * i], pv = s.c[4 * i + 1], vp = s.c[4 * i + 2], vv = s.c[4 * i + 3];
+        const double S = pp + r[i] * r[i];
+        const double il = 1.0 / sqrt(S);
+        const double kp = (pp * il) * il;
+        const double kv = (vp * il) * il;
+        const double innov = z[i] - s.m[i];
+        s.m[i] = s.m[i] + innov * kp;
+        s.m[i + 4] = s.m[i + 4] + innov * kv;
+        s.c[4 * i + 0] = pp - kp * (S * kp);
+        s.c[4 * i + 1] = pv - kp * (S * kv);
+        s.c[4 * i + 2] = vp - kv * (S * kp);
+        s.c[4 * i + 3] = vv - kv * (S * kv);
+    }
+}
+// gating_distance (strongsort_kf.py:191-233, only_position False) against project(confidence=0):
+// the Cholesky factor of the diagonal projected covariance is its square root, z_i = d_i / l_i,
+// and the squares are summed in axis order.
+__host__ __device__ inline double kf_gating_xyah(const double *m, const double *pp4, const double *z) {
+    double acc = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double r = kf_nsa_std(m, i, 0.0);
+        const double l = sqrt(pp4[i] + r * r);
+        const double q = (z[i] - m[i]) / l;
+        acc = i == 0 ? q * q : acc + q * q;
+    }
+    return acc;
+}
+// Track.camera_update (strongsort/sort/track.py:129-138): both corners of the box through the
+// 2x3 warp, mean[:4] rebuilt from them; the covariance is untouched.
+__host__ __device__ inline void kf_camera_update(double *m, const double *H) {
+    const double w0 = m[2] * m[3];
+    const double x1 = m[0] - w0 / 2, y1 = m[1] - m[3] / 2;
+    const double x2 = x1 + w0, y2 = y1 + m[3];
+    const double x1w = (H[0] * x1 + H[1] * y1) + H[2], y1w = (H[3] * x1 + H[4] * y1) + H[5];
+    const double x2w = (H[0] * x2 + H[1] * y2) + H[2], y2w = (H[3] * x2 + H[4] * y2) + H[5];
+    const double w = x2w - x1w, h = y2w - y1w;
+    m[0] = x1w + w / 2;
+    m[1] = y1w + h / 2;
+    m[2] = w / h;
+    m[3] = h;
+}
+
 // ---------------------------------------------------------------- BoT-SORT camera-motion warps
 // STrack.multi_gmc (bot_sort.py:95-111): mean <- kron(I4, R) mean, mean[:2] += t,
 // P <- R8 P R8^T with R8 = kron(I4, R).  R mixes x with y (and w with h, and their velocities),

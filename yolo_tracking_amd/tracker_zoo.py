@@ -56,7 +56,10 @@ def create_tracker(tracker_type, tracker_config, reid_weights, device, half, per
                           iou_threshold=cfg.iou_thresh, delta_t=cfg.delta_t,
                           asso_func=cfg.asso_func, inertia=cfg.inertia, reid=reid)
     if tracker_type == "strongsort":
-        raise NotImplementedError(
-            f"{tracker_type}: not yet on the MI355X path in this build; see DESIGN.md")
+        from .trackers.strongsort import StrongSORT
+        return StrongSORT(reid_weights, device, half, max_dist=cfg.max_dist,
+                          max_iou_dist=cfg.max_iou_dist, max_age=cfg.max_age, n_init=cfg.n_init,
+                          nn_budget=cfg.nn_budget, mc_lambda=cfg.mc_lambda,
+                          ema_alpha=cfg.ema_alpha)
     print("No such tracker")
     exit()
