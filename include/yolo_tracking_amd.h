@@ -803,6 +803,61 @@ int yta_strongsort_update_device(yta_strongsort *engine, const double *d_dets,
                                  const double *d_warps, double *d_out, int *d_out_counts,
                                  int *d_n_tracks);
 int yta_strongsort_sync(yta_strongsort *engine);
+/* Tensor path: device rows in, device rows out, stream-ordered, after yta_bytetrack_update_tensors'
+ * contract.  The frame runs on the engine's stream after everything queued on caller_stream (a
+ * hipStream_t, NULL = the default stream), and caller_stream is made to wait for the frame's last
+ * launch before the call returns; a capturing stream is refused.  Nothing is waited for on the
+ * host.  d_dets: packed rows x1 y1 x2 y2 conf cls of dtype (YTA_F64 / YTA_F32 / YTA_F16),
+ * row_stride (>= 6) elements apart, aligned to the element size only, stream s = the next
+ * det_counts[s] rows; promoted exactly to float64.  d_feats: one feat_dim-wide float32 row per
+ * detection row, feat_stride (>= feat_dim) floats apart, read where they are (columns past
+ * feat_dim are never read).  d_warps: S x 6 float64 on the device or NULL; a row whose first value
+ * is NaN = no camera update for that stream.  d_active: S ints on the device (0 = the stream is
+ * left exactly as it was and reports no row) or NULL.  det_counts (S) and next_id (S ID counters
+ * written before the frame, to the active streams; NULL = keep the device's) are host memory,
+ * copied during the call.  d_rows (16-B aligned): rows_capacity >= sum(det_counts) rows x1 y1 x2
+ * y2 id conf cls det_ind, stream s = rows d_row_offsets[s] .. d_row_offsets[s + 1] (S + 1 ints);
+ * d_row_stream (rows_capacity ints, may be NULL): each row's stream, -1 from d_row_offsets[S] on.
+ * Results are bit-identical to yta_strongsort_update on the promoted values.  Every argument is
+ * checked before anything is enqueued.  The engine never grows: a det_counts[s] > max_dets or a
+ * rows_capacity below sum(det_counts) returns YTA_ERR_CAPACITY with the engine unchanged; a stream
+ * that needs more than track_capacity tracks raises the device flag, which the next
+ * yta_strongsort_sync reports, as for yta_strongsort_update_device. */
+int yta_strongsort_update_tensors(yta_strongsort *engine, void *caller_stream, const void *d_dets,
+                                  int dtype, long long row_stride, const int *det_counts,
+                                  const float *d_feats, long long feat_stride,
+                                  const double *d_warps, const int *d_active,
+                                  const long long *next_id, double *d_rows,
+                                  long long rows_capacity, int *d_row_offsets, int *d_row_stream);
+/* Accounting of the tensor path since create, up to n of 4 int64: frames enqueued, calls that
+ * blocked on the device (yta_strongsort_n_tracks after a tensor frame, or 64 frames in flight),
+ * reserves (always 0: the engine does not grow) and ingest_skipped (always 0: float64 rows are
+ * not special-cased, every frame is widened into the engine's slab). */
+int yta_strongsort_tensor_stats(yta_strongsort *engine, long long *out, int n);
+/* The S per-stream ID counters (sort/tracker.py:59 _next_id) as the device holds them; waits for
+ * the engine's stream. */
+int yta_strongsort_next_ids(yta_strongsort *engine, long long *next_id);
+/* Tracks held per stream (S ints, tentative ones included) after the last host-buffer or tensor
+ * update.  After a tensor frame it waits for that frame's completion event (one counted host
+ * wait) and reads the counts the frame left in page-locked memory; nothing is copied. */
+int yta_strongsort_n_tracks(yta_strongsort *engine, int *n_tracks);
+/* Stream subset of yta_strongsort_update: the n_streams listed streams (stream_ids ascending) are
+ * updated, every other stream is left exactly as it was.  det_offsets (n_streams + 1), warps
+ * (n_streams x 6 or NULL), out_offsets (n_streams + 1) and n_tracks (n_streams, may be NULL) cover
+ * the listed streams in id order. */
+int yta_strongsort_update_streams(yta_strongsort *engine, int n_streams, const int *stream_ids,
+                                  const double *dets, const int *det_offsets, const float *feats,
+                                  const double *warps, double *out, int out_capacity,
+                                  int *out_offsets, int *n_tracks);
+/* yta_strongsort_update_device under a device mask: d_active S ints (0 = the stream's state is
+ * untouched, its d_out_counts entry is 0 and its d_n_tracks entry the count it had) or NULL. */
+int yta_strongsort_update_device_masked(yta_strongsort *engine, const int *d_active,
+                                        const double *d_dets, const int *d_det_counts,
+                                        const float *d_feats, const double *d_warps,
+                                        double *d_out, int *d_out_counts, int *d_n_tracks);
+/* One stream back to a freshly constructed tracker (empty list, id counter 1, empty galleries,
+ * error flag cleared); the others are untouched.  Synchronous. */
+int yta_strongsort_reset_stream(yta_strongsort *engine, int stream);
 /* Tracks of one stream in list order (parity introspection); every pointer but n_tracks may be
  * NULL.  ints: n x 5 (id, hits, age, time_since_update, state 1 tentative / 2 confirmed); mean
  * n x 8; cov n x 64; feat n x feat_dim (features[-1]); gallery_len n; gallery n x nn_budget x

@@ -590,9 +590,114 @@ def run_strongsort(args):
             fh.write(json.dumps(line) + "\n")
 
 
+def run_strongsort_tensors(args):
+    """--tracker strongsort --tensors: update_tensors beside the raw update_device loop, in
+    run_tensors' form: one engine of all S streams per leg, fresh for every repeat; a pre-roll of
+    --warmup frames, then --steps timed frames that end in a wait for the device.  The raw leg
+    reads slabs S x max_dets x (6 | D) staged in HBM and leaves S * track_capacity unpacked rows;
+    the tensor leg gets each frame's packed float64 rows and packed feature rows (read where they
+    are) and hands back packed rows, offsets and row_stream tensors.  Prints one JSON line per leg
+    and repeat, then a summary with tensor / raw of the best runs; the lines are appended to --out
+    (default profiles/strongsort_tensors/bench_<n>.jsonl)."""
+    import torch
+    from yolo_tracking_amd import StrongSortEngine, _lib
+    from yolo_tracking_amd.synth import make_frames
+    S, N, D, B = args.streams, args.n or DEFAULT_N["strongsort"], args.dim, args.budget
+    PRE, K = args.warmup, args.steps
+    F = PRE + K
+    streams = [make_frames(N, F, args.seed + s, emb_dim=D, low_conf_frac=0.0) for s in range(S)]
+    maxd = max(len(d) for st in streams for d, _ in st)
+    dets = np.zeros((F, S, maxd, 6))
+    feats = np.zeros((F, S, maxd, D), np.float32)
+    cnt = np.zeros((F, S), np.int32)
+    for s in range(S):
+        for f, (d, e) in enumerate(streams[s]):
+            cnt[f, s] = len(d)
+            dets[f, s, :len(d)] = d
+            feats[f, s, :len(d)] = e
+    d_dets, d_feats, d_cnt = (torch.from_numpy(x).cuda() for x in (dets, feats, cnt))
+    p_dets = [torch.from_numpy(np.concatenate([streams[s][f][0] for s in range(S)])).cuda()
+              for f in range(F)]
+    p_feats = [torch.from_numpy(np.concatenate([streams[s][f][1] for s in range(S)])
+                                .astype(np.float32)).cuda() for f in range(F)]
+    del dets, feats
+    P = ctypes.c_void_p
+
+    def engine():
+        return StrongSortEngine(S, feat_dim=D, nn_budget=B, track_capacity=args.cap_mult * N,
+                                max_dets=maxd, **STRONGSORT_YAML)
+
+    def timed(step, eng):
+        torch.cuda.synchronize()
+        for f in range(PRE):
+            step(f)
+        torch.cuda.synchronize()
+        eng.sync()
+        t0 = time.perf_counter()
+        for f in range(PRE, F):
+            step(f)
+        t1 = time.perf_counter()   # the host is done enqueueing; the device may not be
+        torch.cuda.synchronize()
+        eng.sync()
+        return time.perf_counter() - t0, 1e3 * (t1 - t0) / K
+
+    def raw_leg():
+        eng = engine()
+        cap, _ = eng.capacity()
+        d_out = torch.empty((S * cap, 8), dtype=torch.float64, device="cuda")
+        d_nout = torch.zeros(S, dtype=torch.int32, device="cuda")
+        fn = eng.lib.yta_strongsort_update_device
+        step = lambda f: _lib.check(fn(eng.handle, P(d_dets[f].data_ptr()),
+                                       P(d_cnt[f].data_ptr()), P(d_feats[f].data_ptr()), None,
+                                       P(d_out.data_ptr()), P(d_nout.data_ptr()), None))
+        el, enq = timed(step, eng)
+        rows = int(d_nout.sum())
+        eng.close()
+        return el, dict(host_enqueue_ms_per_frame=enq, out_rows_last=rows)
+
+    def tensor_leg():
+        eng = engine()
+        keep = [None]
+        step = lambda f: keep.__setitem__(0, eng.update_tensors(
+            p_dets[f], p_feats[f], counts=cnt[f]))
+        el, enq = timed(step, eng)
+        st = eng.tensor_stats()
+        rows = int(keep[0][1][-1])
+        eng.close()
+        return el, dict(host_enqueue_ms_per_frame=enq, out_rows_last=rows, **st)
+
+    lines, best = [], {}
+
+    def emit(rec):
+        rec = dict(rec, tracker="strongsort", streams=S, n=N, dim=D, nn_budget=B,
+                   cap_mult=args.cap_mult, preroll=PRE, steps=K)
+        lines.append(rec)
+        print(json.dumps(rec), flush=True)
+
+    for r in range(args.repeats):
+        for name, leg in (("raw_update_device", raw_leg), ("update_tensors", tensor_leg)):
+            el, extra = leg()
+            rate = S * K / el
+            emit(dict(leg=name, repeat=r, calls_per_s=rate, ms_per_frame=1e3 * el / K, **extra))
+            best[name] = max(best.get(name, 0.0), rate)
+    emit(dict(leg="summary", best_calls_per_s=best,
+              tensor_over_raw=best["update_tensors"] / best["raw_update_device"],
+              extra_us_per_frame=1e6 * S * (1 / best["update_tensors"]
+                                            - 1 / best["raw_update_device"])))
+    out = args.out or os.path.join(REPO, "profiles", "strongsort_tensors", f"bench_{N}.jsonl")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "a") as fh:
+        for rec in lines:
+            fh.write(json.dumps(rec) + "\n")
+    return lines
+
+
 def main():
     args = parse()
     if args.tracker == "strongsort":
+        if args.tensors:
+            run_strongsort_tensors(args)
+            return
         run_strongsort(args)
         return
     if args.tensors:

@@ -223,6 +223,14 @@ _SIGS = {
     "yta_strongsort_update": ([_P, _P, _P, _P, _P, _P, _I, _P, _P], _I),
     "yta_strongsort_update_device": ([_P, _P, _P, _P, _P, _P, _P, _P], _I),
     "yta_strongsort_sync": ([_P], _I),
+    "yta_strongsort_update_tensors": ([_P, _P, _P, _I, _LL, _P, _P, _LL, _P, _P, _P, _P, _LL, _P,
+                                       _P], _I),
+    "yta_strongsort_tensor_stats": ([_P, _P, _I], _I),
+    "yta_strongsort_next_ids": ([_P, _P], _I),
+    "yta_strongsort_n_tracks": ([_P, _P], _I),
+    "yta_strongsort_update_streams": ([_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P], _I),
+    "yta_strongsort_update_device_masked": ([_P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "yta_strongsort_reset_stream": ([_P, _I], _I),
     "yta_strongsort_get_state": ([_P, _I, _P, _P, _P, _P, _P, _P, _P], _I),
     "yta_strongsort_hip_stream": ([_P, _P], _I),
     "yta_lsa_replay": ([_I, _I, _I, _P, _P, _P], _I),

@@ -27,6 +27,12 @@
 //   k_ss_feat    [tracks, S]     EMA feature (track.py:168-174), features of the births, gallery
 //                                ring append (tracker.py:96-106, matching.py:343-358); one wave
 //                                per track
+// All six take an [S] mask (SsArgs::active; null: every stream): a masked stream's blocks return
+// before their first barrier and leave its state untouched (update_streams, update_device_masked,
+// update_tensors' `active`).  A tensor frame (yta_strongsort_update_tensors) wraps them in
+// ss_tensors.hpp's three: k_ss_ingest in front (counts, offsets, ID counters and the widened
+// detection rows; the feature rows stay where the caller has them, k_ss_norm reads them through
+// SsArgs::foff / fstride), k_ss_out_offsets and k_ss_pack_rows behind.
 //
 // Float32 order (the reference's np.dot / np.linalg.norm fix none; tests/strongsort_oracle.py
 // restates this one, device against restatement is bit-exact):
@@ -43,10 +49,15 @@
 // ordered array of slots, so deleting a track moves no gallery.  Stage 2's rows after the
 // unconfirmed tracks are in ascending list position (the reference iterates a Python set there).
 #include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
 #include <vector>
 
 #include "kf_xyah.hpp"
 #include "lsa_replay.hpp"
+#include "ss_tensors.hpp"
+#include "subset.hpp"
 
 using namespace yta;
 
@@ -68,7 +79,10 @@ struct SsArgs {
     float ema_a, ema_b;
     const double *dets;     // S x MAXD x 6
     const int *ndet;        // S
-    const float *feats;     // S x MAXD x D
+    const float *feats;     // S x MAXD x D; with foff: packed rows, fstride floats apart
+    const int *foff;        // S + 1 row offsets of the packed feats (the tensor path) or null
+    long long fstride;
+    const int *active;      // S (0: the stream is left exactly as it is) or null: every stream
     const double *warps;    // S x 6 (a NaN first value: no camera update) or null
     double *kf;             // S x CAP x 24, by slot
     int *ti;                // S x CAP x T_N
@@ -125,6 +139,7 @@ __device__ __forceinline__ void wave_normalize(const float *src, float *dst, int
 __global__ __launch_bounds__(SS_T) void k_ss_pre(SsArgs a) {
     __shared__ int wsum[16];
     const int s = blockIdx.x, t = threadIdx.x;
+    if (a.active && !a.active[s]) return;                  // block-uniform, before any barrier
     const long long tb = (long long)s * a.CAP, db = (long long)s * a.MAXD;
     int *hdr = a.hdr + s * H_N;
     const int n = hdr[H_NTRK], m = a.ndet[s];
@@ -165,9 +180,10 @@ __global__ __launch_bounds__(SS_T) void k_ss_pre(SsArgs a) {
 __global__ __launch_bounds__(SS_T) void k_ss_norm(SsArgs a) {
     const int s = blockIdx.y;
     const int j = blockIdx.x * (SS_T / WAVE) + threadIdx.x / WAVE;
-    if (j >= a.ndet[s]) return;
+    if ((a.active && !a.active[s]) || j >= a.ndet[s]) return;
     const long long off = ((long long)s * a.MAXD + j) * a.D;
-    wave_normalize(a.feats + off, a.fn + off, a.D);
+    const float *src = a.foff ? a.feats + ((long long)a.foff[s] + j) * a.fstride : a.feats + off;
+    wave_normalize(src, a.fn + off, a.D);
 }
 
 // ------------------------------------------------------------------------------------ k_ss_gal
@@ -221,6 +237,7 @@ __device__ __forceinline__ float gal_wave_min(const float *g, int len, int D, co
 template <bool VEC>
 __global__ __launch_bounds__(SS_T) void k_ss_gal(SsArgs a) {
     const int s = blockIdx.z, r = blockIdx.y;
+    if (a.active && !a.active[s]) return;
     const int *hdr = a.hdr + s * H_N;
     const int m = a.ndet[s];
     if (r >= hdr[H_NCONF]) return;
@@ -290,6 +307,7 @@ __global__ __launch_bounds__(LSA_T) void k_ss_match(SsArgs a, int ws_n) {
     __shared__ LsaShared sh;
     __shared__ int wsum[16];
     const int s = blockIdx.x, t = threadIdx.x;
+    if (a.active && !a.active[s]) return;                  // block-uniform, before any barrier
     const long long tb = (long long)s * a.CAP, db = (long long)s * a.MAXD;
     int *hdr = a.hdr + s * H_N;
     const int n = hdr[H_NTRK], m = a.ndet[s], nconf = hdr[H_NCONF];
@@ -353,6 +371,13 @@ __global__ __launch_bounds__(LSA_T) void k_ss_match(SsArgs a, int ws_n) {
 __global__ __launch_bounds__(SS_T) void k_ss_apply(SsArgs a) {
     __shared__ int wsum[16];
     const int s = blockIdx.x, t = threadIdx.x;
+    if (a.active && !a.active[s]) {   // block-uniform, before any barrier: no rows, the old count
+        if (t == 0) {
+            a.nout[s] = 0;
+            a.ntrk_out[s] = a.hdr[s * H_N + H_NTRK];
+        }
+        return;
+    }
     const long long tb = (long long)s * a.CAP, db = (long long)s * a.MAXD;
     int *hdr = a.hdr + s * H_N;
     const int n = hdr[H_NTRK], nb = hdr[H_NBIRTH], nf0 = hdr[H_NFREE], next0 = hdr[H_NEXT];
@@ -461,7 +486,7 @@ __global__ __launch_bounds__(SS_T) void k_ss_apply(SsArgs a) {
 __global__ __launch_bounds__(SS_T) void k_ss_feat(SsArgs a) {
     const int s = blockIdx.y, lane = lane_id();
     const int k = blockIdx.x * (SS_T / WAVE) + threadIdx.x / WAVE;
-    if (k >= a.hdr[s * H_N + H_NTRK]) return;
+    if ((a.active && !a.active[s]) || k >= a.hdr[s * H_N + H_NTRK]) return;
     const long long tb = (long long)s * a.CAP, db = (long long)s * a.MAXD;
     const int slot = a.order[tb + k], act = a.sact[tb + slot];
     float *f = a.feat + (tb + slot) * a.D;
@@ -482,8 +507,9 @@ __global__ __launch_bounds__(SS_T) void k_ss_feat(SsArgs a) {
     if (lane == 0) a.gcnt[tb + slot] = cnt + 1 >= 2 * a.B ? cnt + 1 - a.B : cnt + 1;
 }
 
-__global__ void k_ss_reset(SsArgs a) {
-    const int s = blockIdx.x;
+// streams s0 .. s0 + gridDim.x - 1 back to a freshly constructed tracker
+__global__ void k_ss_reset(SsArgs a, int s0) {
+    const int s = s0 + blockIdx.x;
     const long long tb = (long long)s * a.CAP;
     for (int k = threadIdx.x; k < a.CAP; k += blockDim.x) {
         a.freel[tb + k] = a.CAP - 1 - k;                    // slot 0 is handed out first
@@ -568,6 +594,21 @@ int lsa_lds_setup(const void *fn, size_t bytes) {
     return YTA_OK;
 }
 
+// The tensor path's host state (yta_strongsort_update_tensors): a ring of slots, one per frame in
+// flight.  A slot is two events and one page-locked mapped block: S counts and S + 1 offsets in,
+// S track counts back (k_ss_pack_rows), S ID counters in.
+struct SsTensorSlot {
+    hipEvent_t in = nullptr, done = nullptr;
+    void *h = nullptr;
+    int *h_counts = nullptr, *h_offs = nullptr, *h_live = nullptr;
+    long long *h_nid = nullptr;
+    int *m_counts = nullptr, *m_offs = nullptr, *m_live = nullptr;   // the device's view
+    long long *m_nid = nullptr;
+    long long seq = -1;   // enqueue order (-1: never used)
+};
+enum { STS_FRAMES, STS_HOST_WAITS, STS_RESERVES, STS_INGEST_SKIPPED, STS_N };
+constexpr size_t SS_RING_MAX = 64;   // frames in flight before a call waits for the oldest
+
 }  // namespace
 
 struct yta_strongsort {
@@ -575,25 +616,47 @@ struct yta_strongsort {
     SsArgs a{};
     DevMem mem;
     hipStream_t stream = nullptr;
-    // staging of the host-buffer form
+    // staging of the host-buffer form; the tensor path widens into d_dets and counts into d_ndet
     double *d_dets = nullptr, *d_warps = nullptr, *d_out = nullptr;
     float *d_feats = nullptr;
     int *d_ndet = nullptr, *d_nout = nullptr, *d_ntrk = nullptr;
+    int *d_off = nullptr;   // S + 1 detection offsets of a tensor frame (k_ss_ingest)
     size_t lds = 0;
     int ws_n = 0;
+    StreamMask mask;        // stream-subset updates (subset.hpp)
+    std::vector<SsTensorSlot *> ring;
+    SsTensorSlot *newest = nullptr;   // the last tensor frame, while its counts are the newest
+    std::vector<int> ntrk;            // tracks per stream after the last update the host saw
+    long long stat[STS_N] = {};
+    long long seq = 0;
     ~yta_strongsort() {
+        for (SsTensorSlot *p : ring) {
+            if (p->in) (void)hipEventDestroy(p->in);
+            if (p->done) (void)hipEventDestroy(p->done);
+            if (p->h) (void)hipHostFree(p->h);
+            delete p;
+        }
+        mask.release();
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
 
 namespace {
 
+// One frame on the engine's stream under the mask staged for it (subset.hpp; none: every stream).
+// d_foff / fstride: the feature rows are packed, fstride floats apart, stream s from row d_foff[s]
+// (null: the slab S x MAXD x D).
 int ss_launch(yta_strongsort *e, const double *d_dets, const int *d_ndet, const float *d_feats,
-              const double *d_warps, double *d_out, int *d_nout, int *d_ntrk) {
+              const double *d_warps, double *d_out, int *d_nout, int *d_ntrk,
+              const int *d_foff = nullptr, long long fstride = 0) {
     SsArgs a = e->a;
+    int rc = e->mask.stage(a.S, e->stream, &a.active);
+    if (rc) return rc;
     a.dets = d_dets;
     a.ndet = d_ndet;
     a.feats = d_feats;
+    a.foff = d_foff;
+    a.fstride = fstride;
     a.warps = d_warps;
     a.out = d_out;
     a.nout = d_nout;
@@ -623,6 +686,114 @@ int ss_check_err(yta_strongsort *e) {
                   "must be reset)", s, e->a.CAP);
         YTA_CHECK(!err, YTA_ERR_INVALID, "strongsort: stream %d: non-finite cost matrix", s);
     }
+    return YTA_OK;
+}
+
+// After a host wait on the engine's stream: the newest tensor frame's track counts (stored into
+// its slot by k_ss_pack_rows) become the host's.
+void ss_take_live(yta_strongsort *e) {
+    if (!e->newest) return;
+    memcpy(e->ntrk.data(), e->newest->h_live, sizeof(int) * e->a.S);
+    e->newest = nullptr;
+}
+
+// The host-buffer update on all S streams (det_offsets: S + 1), under e->mask when one is set.
+// Runs on the engine's stream, so after every tensor frame in flight.
+int ss_update_host(yta_strongsort *e, const double *dets, const int *det_offsets,
+                   const float *feats, const double *warps, double *out, int out_capacity,
+                   int *out_offsets) {
+    const SsArgs &a = e->a;
+    std::vector<int> nd(a.S);
+    for (int s = 0; s < a.S; ++s) {
+        nd[s] = det_offsets[s + 1] - det_offsets[s];
+        YTA_CHECK(nd[s] >= 0, YTA_ERR_INVALID, "det_offsets must not decrease");
+        YTA_CHECK(nd[s] <= a.MAXD, YTA_ERR_CAPACITY, "stream %d: %d detections > max_dets = %d", s,
+                  nd[s], a.MAXD);
+        YTA_CHECK(nd[s] == 0 || (dets && feats), YTA_ERR_INVALID, "null detections / features");
+    }
+    for (int s = 0; s < a.S; ++s) {
+        if (!nd[s]) continue;
+        YTA_HIP(hipMemcpyAsync(e->d_dets + (size_t)s * a.MAXD * 6, dets + (size_t)det_offsets[s] * 6,
+                               sizeof(double) * 6 * nd[s], hipMemcpyHostToDevice, e->stream));
+        YTA_HIP(hipMemcpyAsync(e->d_feats + (size_t)s * a.MAXD * a.D,
+                               feats + (size_t)det_offsets[s] * a.D, sizeof(float) * a.D * nd[s],
+                               hipMemcpyHostToDevice, e->stream));
+    }
+    YTA_HIP(hipMemcpyAsync(e->d_ndet, nd.data(), sizeof(int) * a.S, hipMemcpyHostToDevice, e->stream));
+    if (warps)
+        YTA_HIP(hipMemcpyAsync(e->d_warps, warps, sizeof(double) * 6 * a.S, hipMemcpyHostToDevice,
+                               e->stream));
+    YTA_HIP(host_wait(e->stream));   // nd / the caller's buffers are read by now
+    ss_take_live(e);
+    int rc = ss_launch(e, e->d_dets, e->d_ndet, e->d_feats, warps ? e->d_warps : nullptr, e->d_out,
+                       e->d_nout, e->d_ntrk);
+    if (rc) return rc;
+    std::vector<int> no(a.S), nt(a.S);
+    YTA_HIP(hipMemcpyAsync(no.data(), e->d_nout, sizeof(int) * a.S, hipMemcpyDeviceToHost, e->stream));
+    YTA_HIP(hipMemcpyAsync(nt.data(), e->d_ntrk, sizeof(int) * a.S, hipMemcpyDeviceToHost, e->stream));
+    rc = ss_check_err(e);
+    if (rc) return rc;
+    out_offsets[0] = 0;
+    for (int s = 0; s < a.S; ++s) out_offsets[s + 1] = out_offsets[s] + no[s];
+    YTA_CHECK(out_offsets[a.S] <= out_capacity, YTA_ERR_CAPACITY,
+              "out_capacity %d < %d output rows", out_capacity, out_offsets[a.S]);
+    YTA_CHECK(out_offsets[a.S] == 0 || out, YTA_ERR_INVALID, "null out");
+    for (int s = 0; s < a.S; ++s)
+        if (no[s])
+            YTA_HIP(hipMemcpyAsync(out + (size_t)out_offsets[s] * 8, e->d_out + (size_t)s * a.CAP * 8,
+                                   sizeof(double) * 8 * no[s], hipMemcpyDeviceToHost, e->stream));
+    YTA_HIP(host_wait(e->stream));
+    e->ntrk = nt;
+    return YTA_OK;
+}
+
+int ss_slot_new(yta_strongsort *e, SsTensorSlot **out) {
+    auto *p = new (std::nothrow) SsTensorSlot();
+    YTA_CHECK(p, YTA_ERR_NOMEM, "out of host memory");
+    e->ring.push_back(p);   // owned from here on (the engine's destructor)
+    const size_t S = e->a.S;
+    YTA_HIP(hipEventCreateWithFlags(&p->in, hipEventDisableTiming));
+    YTA_HIP(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
+    // S ID counters first (8-B aligned), then counts, offsets, track counts
+    YTA_HIP(hipHostMalloc(&p->h, sizeof(long long) * S + sizeof(int) * (3 * S + 1),
+                          hipHostMallocMapped | hipHostMallocCoherent));
+    void *m = nullptr;
+    YTA_HIP(hipHostGetDevicePointer(&m, p->h, 0));
+    auto carve = [S](void *base, long long **nid, int **counts, int **offs, int **live) {
+        *nid = (long long *)base;
+        *counts = (int *)(*nid + S);
+        *offs = *counts + S;
+        *live = *offs + S + 1;
+    };
+    carve(p->h, &p->h_nid, &p->h_counts, &p->h_offs, &p->h_live);
+    carve(m, &p->m_nid, &p->m_counts, &p->m_offs, &p->m_live);
+    *out = p;
+    return YTA_OK;
+}
+
+bool ss_slot_done(SsTensorSlot *p) {
+    if (p->seq < 0) return true;   // never used
+    if (hipEventQuery(p->done) == hipSuccess) return true;
+    (void)hipGetLastError();   // hipErrorNotReady
+    return false;
+}
+
+// A slot no queued frame reads: one whose frame has run (not the newest: n_tracks() reads its
+// counts), else a new one; with SS_RING_MAX frames in flight the call waits for the oldest.
+int ss_slot_acquire(yta_strongsort *e, SsTensorSlot **out) {
+    SsTensorSlot *oldest = nullptr;
+    for (SsTensorSlot *p : e->ring) {
+        if (!p->m_live || p == e->newest) continue;   // m_live null: its allocation failed part way
+        if (ss_slot_done(p)) {
+            *out = p;
+            return YTA_OK;
+        }
+        if (!oldest || p->seq < oldest->seq) oldest = p;
+    }
+    if (e->ring.size() < SS_RING_MAX || !oldest) return ss_slot_new(e, out);
+    ++e->stat[STS_HOST_WAITS];
+    YTA_HIP(hipEventSynchronize(oldest->done));
+    *out = oldest;
     return YTA_OK;
 }
 
@@ -702,7 +873,9 @@ int yta_strongsort_create(int device, int n_streams, int track_capacity, int max
     SS_GET(e->d_ndet, S);
     SS_GET(e->d_nout, S);
     SS_GET(e->d_ntrk, S);
+    SS_GET(e->d_off, S + 1);
 #undef SS_GET
+    e->ntrk.assign(S, 0);
     a.nout = e->d_nout;
     a.ntrk_out = e->d_ntrk;
     hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
@@ -734,9 +907,25 @@ int yta_strongsort_reset(yta_strongsort *e) {
     YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
     int rc = select_device(e->device);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ss_reset, dim3(e->a.S), dim3(256), 0, e->stream, e->a);
+    hipLaunchKernelGGL(k_ss_reset, dim3(e->a.S), dim3(256), 0, e->stream, e->a, 0);
+    YTA_HIP(hipGetLastError());
+    YTA_HIP(host_wait(e->stream));   // tensor frames in flight have run and are wiped
+    e->newest = nullptr;
+    e->ntrk.assign(e->a.S, 0);
+    return YTA_OK;
+}
+
+int yta_strongsort_reset_stream(yta_strongsort *e, int stream) {
+    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
+    YTA_CHECK(stream >= 0 && stream < e->a.S, YTA_ERR_INVALID, "stream %d outside 0..%d", stream,
+              e->a.S - 1);
+    int rc = select_device(e->device);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ss_reset, dim3(1), dim3(256), 0, e->stream, e->a, stream);
     YTA_HIP(hipGetLastError());
     YTA_HIP(host_wait(e->stream));
+    ss_take_live(e);   // every tensor frame has run: the other streams' counts are in its slot
+    e->ntrk[stream] = 0;
     return YTA_OK;
 }
 
@@ -754,47 +943,35 @@ int yta_strongsort_update(yta_strongsort *e, const double *dets, const int *det_
                           const float *feats, const double *warps, double *out, int out_capacity,
                           int *out_offsets, int *n_tracks) {
     YTA_CHECK(e && det_offsets && out_offsets, YTA_ERR_INVALID, "null argument");
-    const SsArgs &a = e->a;
     int rc = select_device(e->device);
     if (rc) return rc;
-    std::vector<int> nd(a.S);
-    for (int s = 0; s < a.S; ++s) {
-        nd[s] = det_offsets[s + 1] - det_offsets[s];
-        YTA_CHECK(nd[s] >= 0, YTA_ERR_INVALID, "det_offsets must not decrease");
-        YTA_CHECK(nd[s] <= a.MAXD, YTA_ERR_CAPACITY, "stream %d: %d detections > max_dets = %d", s,
-                  nd[s], a.MAXD);
-        YTA_CHECK(nd[s] == 0 || (dets && feats), YTA_ERR_INVALID, "null detections / features");
-        if (!nd[s]) continue;
-        YTA_HIP(hipMemcpyAsync(e->d_dets + (size_t)s * a.MAXD * 6, dets + (size_t)det_offsets[s] * 6,
-                               sizeof(double) * 6 * nd[s], hipMemcpyHostToDevice, e->stream));
-        YTA_HIP(hipMemcpyAsync(e->d_feats + (size_t)s * a.MAXD * a.D,
-                               feats + (size_t)det_offsets[s] * a.D, sizeof(float) * a.D * nd[s],
-                               hipMemcpyHostToDevice, e->stream));
-    }
-    YTA_HIP(hipMemcpyAsync(e->d_ndet, nd.data(), sizeof(int) * a.S, hipMemcpyHostToDevice, e->stream));
-    if (warps)
-        YTA_HIP(hipMemcpyAsync(e->d_warps, warps, sizeof(double) * 6 * a.S, hipMemcpyHostToDevice,
-                               e->stream));
-    YTA_HIP(host_wait(e->stream));   // nd / the caller's buffers are read by now
-    rc = ss_launch(e, e->d_dets, e->d_ndet, e->d_feats, warps ? e->d_warps : nullptr, e->d_out,
-                   e->d_nout, e->d_ntrk);
+    rc = ss_update_host(e, dets, det_offsets, feats, warps, out, out_capacity, out_offsets);
     if (rc) return rc;
-    std::vector<int> no(a.S), nt(a.S);
-    YTA_HIP(hipMemcpyAsync(no.data(), e->d_nout, sizeof(int) * a.S, hipMemcpyDeviceToHost, e->stream));
-    YTA_HIP(hipMemcpyAsync(nt.data(), e->d_ntrk, sizeof(int) * a.S, hipMemcpyDeviceToHost, e->stream));
-    rc = ss_check_err(e);
+    if (n_tracks) memcpy(n_tracks, e->ntrk.data(), sizeof(int) * e->a.S);
+    return YTA_OK;
+}
+
+int yta_strongsort_update_streams(yta_strongsort *e, int n_streams, const int *stream_ids,
+                                  const double *dets, const int *det_offsets, const float *feats,
+                                  const double *warps, double *out, int out_capacity,
+                                  int *out_offsets, int *n_tracks) {
+    YTA_CHECK(e && out_offsets, YTA_ERR_INVALID, "null argument");
+    int rc = select_device(e->device);
     if (rc) return rc;
-    out_offsets[0] = 0;
-    for (int s = 0; s < a.S; ++s) out_offsets[s + 1] = out_offsets[s] + no[s];
-    YTA_CHECK(out_offsets[a.S] <= out_capacity, YTA_ERR_CAPACITY,
-              "out_capacity %d < %d output rows", out_capacity, out_offsets[a.S]);
-    for (int s = 0; s < a.S; ++s)
-        if (no[s])
-            YTA_HIP(hipMemcpyAsync(out + (size_t)out_offsets[s] * 8, e->d_out + (size_t)s * a.CAP * 8,
-                                   sizeof(double) * 8 * no[s], hipMemcpyDeviceToHost, e->stream));
-    YTA_HIP(host_wait(e->stream));
+    const int S = e->a.S;
+    std::vector<int> mask, off, full_oo(S + 1, 0);
+    rc = subset_expand(S, n_streams, stream_ids, det_offsets, mask, off);
+    if (rc) return rc;
+    std::vector<double> w;   // a stream not listed gets no camera update either way
+    if (warps) w = subset_spread<double>(S, n_streams, stream_ids, warps, 6, NAN);
+    e->mask.req_host = mask.data();
+    rc = ss_update_host(e, dets, off.data(), feats, warps ? w.data() : nullptr, out, out_capacity,
+                        full_oo.data());
+    e->mask.req_host = nullptr;
+    if (rc) return rc;
+    subset_compact(n_streams, stream_ids, full_oo, out_offsets);
     if (n_tracks)
-        for (int s = 0; s < a.S; ++s) n_tracks[s] = nt[s];
+        for (int k = 0; k < n_streams; ++k) n_tracks[k] = e->ntrk[stream_ids[k]];
     return YTA_OK;
 }
 
@@ -809,11 +986,143 @@ int yta_strongsort_update_device(yta_strongsort *e, const double *d_dets, const 
                      d_n_tracks ? d_n_tracks : e->d_ntrk);
 }
 
+int yta_strongsort_update_device_masked(yta_strongsort *e, const int *d_active,
+                                        const double *d_dets, const int *d_det_counts,
+                                        const float *d_feats, const double *d_warps,
+                                        double *d_out, int *d_out_counts, int *d_n_tracks) {
+    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
+    e->mask.req_dev = d_active;
+    const int rc = yta_strongsort_update_device(e, d_dets, d_det_counts, d_feats, d_warps, d_out,
+                                                d_out_counts, d_n_tracks);
+    e->mask.req_dev = nullptr;
+    return rc;
+}
+
+int yta_strongsort_update_tensors(yta_strongsort *e, void *caller_stream, const void *d_dets,
+                                  int dtype, long long row_stride, const int *det_counts,
+                                  const float *d_feats, long long feat_stride,
+                                  const double *d_warps, const int *d_active,
+                                  const long long *next_id, double *d_rows,
+                                  long long rows_capacity, int *d_row_offsets, int *d_row_stream) {
+    YTA_CHECK(e && det_counts && d_row_offsets, YTA_ERR_INVALID, "null argument");
+    YTA_CHECK(dtype == YTA_F64 || dtype == YTA_F32 || dtype == YTA_F16, YTA_ERR_INVALID,
+              "dtype %d is none of YTA_F64, YTA_F32, YTA_F16", dtype);
+    YTA_CHECK(row_stride >= 6, YTA_ERR_INVALID, "row_stride %lld < 6", row_stride);
+    const SsArgs &a = e->a;
+    const int S = a.S;
+    long long total = 0;
+    for (int s = 0; s < S; ++s) {
+        YTA_CHECK(det_counts[s] >= 0, YTA_ERR_INVALID, "det_counts[%d] is negative", s);
+        YTA_CHECK(det_counts[s] <= a.MAXD, YTA_ERR_CAPACITY,
+                  "stream %d: %d detections > max_dets = %d", s, det_counts[s], a.MAXD);
+        total += det_counts[s];
+    }
+    YTA_CHECK(total <= 0x7fffffffLL, YTA_ERR_INVALID, "%lld detections in one frame", total);
+    const size_t esz = dtype == YTA_F64 ? 8 : dtype == YTA_F32 ? 4 : 2;
+    YTA_CHECK(total == 0 || (d_dets && (uintptr_t)d_dets % esz == 0), YTA_ERR_INVALID,
+              "d_dets null or not aligned to its element size");
+    // every output row is a track matched to one of this frame's detections
+    YTA_CHECK(rows_capacity >= total, YTA_ERR_CAPACITY,
+              "d_rows holds %lld rows, the call needs sum(det_counts) = %lld", rows_capacity, total);
+    YTA_CHECK(total == 0 || (d_rows && (uintptr_t)d_rows % 16 == 0), YTA_ERR_INVALID,
+              "d_rows null or not 16-byte aligned");
+    YTA_CHECK(total == 0 ||
+                  (d_feats && (uintptr_t)d_feats % sizeof(float) == 0 && feat_stride >= a.D),
+              YTA_ERR_INVALID, "d_feats null, misaligned or feat_stride < feat_dim");
+    YTA_CHECK(!d_warps || (uintptr_t)d_warps % sizeof(double) == 0, YTA_ERR_INVALID,
+              "d_warps misaligned");
+    int rc = select_device(e->device);
+    if (rc) return rc;
+    const hipStream_t cs = (hipStream_t)caller_stream;
+    {   // the cross-stream waits must not end up in somebody's graph
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(cs, &st) != hipSuccess) (void)hipGetLastError();
+        YTA_CHECK(st == hipStreamCaptureStatusNone, YTA_ERR_INVALID, "caller_stream is capturing");
+    }
+    SsTensorSlot *p = nullptr;
+    rc = ss_slot_acquire(e, &p);
+    if (rc) return rc;
+    memcpy(p->h_counts, det_counts, sizeof(int) * S);
+    p->h_offs[0] = 0;
+    for (int s = 0; s < S; ++s) p->h_offs[s + 1] = p->h_offs[s] + det_counts[s];
+    if (next_id) memcpy(p->h_nid, next_id, sizeof(long long) * S);
+    p->seq = ++e->seq;
+    e->newest = p;
+    ++e->stat[STS_FRAMES];
+    // the engine stream after everything queued on the caller's so far
+    YTA_HIP(hipEventRecord(p->in, cs));
+    YTA_HIP(hipStreamWaitEvent(e->stream, p->in, 0));
+    {
+        const int cps = (3 * a.MAXD + SS_ING_T - 1) / SS_ING_T;
+        const unsigned grid = 1u + (total ? (unsigned)S * cps : 0u);
+        const long long *nid = next_id ? p->m_nid : nullptr;
+#define SS_INGEST(T)                                                                             \
+    hipLaunchKernelGGL(k_ss_ingest<T>, dim3(grid), dim3(SS_ING_T), 0, e->stream,                 \
+                       (const T *)d_dets, row_stride, p->m_counts, p->m_offs, nid, d_active, S,  \
+                       a.MAXD, cps, e->d_ndet, e->d_off, a.hdr, (int)H_N, (int)H_NEXT, e->d_dets)
+        if (dtype == YTA_F64) SS_INGEST(double);
+        else if (dtype == YTA_F32) SS_INGEST(float);
+        else SS_INGEST(_Float16);
+#undef SS_INGEST
+        YTA_HIP(hipGetLastError());
+    }
+    e->mask.req_dev = d_active;
+    rc = ss_launch(e, e->d_dets, e->d_ndet, d_feats, d_warps, e->d_out, e->d_nout, e->d_ntrk,
+                   e->d_off, feat_stride);
+    e->mask.req_dev = nullptr;
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ss_out_offsets, dim3(1), dim3(SS_OFFS_T), 0, e->stream, e->d_nout, S,
+                       a.CAP, d_row_offsets);
+    hipLaunchKernelGGL(k_ss_pack_rows, dim3(S), dim3(256), 0, e->stream, e->d_out,
+                       (long long)a.CAP, e->d_ntrk, S, d_row_offsets, d_rows, rows_capacity,
+                       d_row_stream, p->m_live);
+    YTA_HIP(hipGetLastError());
+    // the caller's stream after the frame's last launch: its later work sees the outputs and may
+    // free or overwrite the inputs
+    YTA_HIP(hipEventRecord(p->done, e->stream));
+    YTA_HIP(hipStreamWaitEvent(cs, p->done, 0));
+    return YTA_OK;
+}
+
+int yta_strongsort_tensor_stats(yta_strongsort *e, long long *out, int n) {
+    YTA_CHECK(e && (out || n <= 0), YTA_ERR_INVALID, "null argument");
+    for (int k = 0; k < n && k < STS_N; ++k) out[k] = e->stat[k];
+    return YTA_OK;
+}
+
+int yta_strongsort_next_ids(yta_strongsort *e, long long *next_id) {
+    YTA_CHECK(e && next_id, YTA_ERR_INVALID, "null argument");
+    int rc = select_device(e->device);
+    if (rc) return rc;
+    std::vector<int> hdr((size_t)e->a.S * H_N);
+    YTA_HIP(hipMemcpyAsync(hdr.data(), e->a.hdr, sizeof(int) * hdr.size(), hipMemcpyDeviceToHost,
+                           e->stream));
+    YTA_HIP(host_wait(e->stream));
+    ss_take_live(e);
+    for (int s = 0; s < e->a.S; ++s) next_id[s] = hdr[(size_t)s * H_N + H_NEXT];
+    return YTA_OK;
+}
+
+int yta_strongsort_n_tracks(yta_strongsort *e, int *n_tracks) {
+    YTA_CHECK(e && n_tracks, YTA_ERR_INVALID, "null argument");
+    if (e->newest) {   // page-locked counts of the newest tensor frame: wait for its event only
+        int rc = select_device(e->device);
+        if (rc) return rc;
+        ++e->stat[STS_HOST_WAITS];
+        YTA_HIP(hipEventSynchronize(e->newest->done));
+        ss_take_live(e);
+    }
+    memcpy(n_tracks, e->ntrk.data(), sizeof(int) * e->a.S);
+    return YTA_OK;
+}
+
 int yta_strongsort_sync(yta_strongsort *e) {
     YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
     int rc = select_device(e->device);
     if (rc) return rc;
-    return ss_check_err(e);
+    rc = ss_check_err(e);
+    ss_take_live(e);   // waited either way
+    return rc;
 }
 
 int yta_strongsort_get_state(yta_strongsort *e, int stream, int *n_tracks, long long *ints,

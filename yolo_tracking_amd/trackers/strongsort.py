@@ -14,17 +14,21 @@ The ReID forward pass (:68 get_features) and the ECC estimate (:63) are inputs o
 object with get_features is passed as the weights, or `cmc=` is given.
 """
 import ctypes
+import inspect
 
 import numpy as np
 
 from .. import _lib
+from ._streams import StreamSubset
+from ._tensors import TensorFrame, TensorPath, is_cuda_tensor, takes_device_frames
 from ..appearance import build_reid
 from ..motion.cmc import get_cmc_method
 
 
-class StrongSortEngine:
+class StrongSortEngine(StreamSubset, TensorPath):
     """S independent StrongSORT streams sharing one device engine; one update() = one
     StrongSORT.update (strong_sort.py:42-99) per stream after its features and warp are known."""
+    _abi = "strongsort"
 
     def __init__(self, n_streams=1, feat_dim=512, max_dist=0.2, max_iou_dist=0.7, max_age=30,
                  n_init=1, nn_budget=100, mc_lambda=0.995, ema_alpha=0.9, device=0,
@@ -48,7 +52,6 @@ class StrongSortEngine:
         self._h = h
         self._out = np.empty((0, 8), dtype=np.float64)
         self._out_off = np.zeros(self.n_streams + 1, dtype=np.int32)
-        self._n_tracks = np.zeros(self.n_streams, dtype=np.int32)
 
     @property
     def handle(self):
@@ -67,7 +70,11 @@ class StrongSortEngine:
 
     def reset(self):
         _lib.check(self.lib.yta_strongsort_reset(self._h))
-        self._n_tracks[:] = 0
+
+    def reset_stream(self, stream):
+        """Reset one stream to a freshly constructed tracker (ids restart at 1, empty galleries);
+        the others are untouched."""
+        _lib.check(self.lib.yta_strongsort_reset_stream(self._h, int(stream)))
 
     def capacity(self):
         c, d = ctypes.c_int(), ctypes.c_int()
@@ -77,16 +84,18 @@ class StrongSortEngine:
 
     def n_tracks(self):
         """Tracks each stream holds (tentative ones included): the reference runs its camera
-        motion estimator only on frames where this is >= 1 (strong_sort.py:62)."""
-        return self._n_tracks.copy()
+        motion estimator only on frames where this is >= 1 (strong_sort.py:62).  The counts are
+        those after the last update() / update_streams() / update_tensors().  After a tensor frame
+        this waits for that frame's completion event and reads the counts it left in page-locked
+        memory: one host wait (counted in tensor_stats()["host_waits"]), no copy."""
+        n = np.zeros(self.n_streams, dtype=np.int32)
+        _lib.check(self.lib.yta_strongsort_n_tracks(self._h, _lib.ptr(n)))
+        return n
 
-    def update(self, dets_per_stream, feats_per_stream, warps=None):
-        """dets_per_stream: S float64 (M_s, 6) rows x1 y1 x2 y2 conf cls; feats_per_stream: S
-        float32 (M_s, D), the get_features rows of every detection; warps: None or S entries, each
-        a 2x3 warp or None (no camera update for that stream).  Returns S (K_s, 8) arrays
-        [x1, y1, x2, y2, id, conf, cls, det_ind]."""
-        S = self.n_streams
-        assert len(dets_per_stream) == S
+    def _pack_host(self, dets_per_stream, feats_per_stream, warps):
+        """The host-buffer call's packed detections, offsets, feature rows and S x 6 warps (NaN
+        rows for the streams without one) for n listed streams."""
+        S = len(dets_per_stream)
         dets = [np.asarray(d, dtype=np.float64).reshape(-1, 6) for d in dets_per_stream]
         off = np.zeros(S + 1, dtype=np.int32)
         np.cumsum([len(d) for d in dets], out=off[1:])
@@ -114,11 +123,72 @@ class StrongSortEngine:
         need = max(min(int(off[-1]), cap * S), 1)   # an output row is matched to a detection
         if len(self._out) < need:
             self._out = np.empty((2 * need, 8), dtype=np.float64)
+        return packed, off, feats, w
+
+    def update(self, dets_per_stream, feats_per_stream, warps=None):
+        """dets_per_stream: S float64 (M_s, 6) rows x1 y1 x2 y2 conf cls; feats_per_stream: S
+        float32 (M_s, D), the get_features rows of every detection; warps: None or S entries, each
+        a 2x3 warp or None (no camera update for that stream).  Returns S (K_s, 8) arrays
+        [x1, y1, x2, y2, id, conf, cls, det_ind]."""
+        S = self.n_streams
+        assert len(dets_per_stream) == S
+        packed, off, feats, w = self._pack_host(dets_per_stream, feats_per_stream, warps)
         _lib.check(self.lib.yta_strongsort_update(
             self._h, _lib.ptr(packed), _lib.ptr(off), _lib.ptr(feats), _lib.ptr(w),
-            _lib.ptr(self._out), len(self._out), _lib.ptr(self._out_off), _lib.ptr(self._n_tracks)))
+            _lib.ptr(self._out), len(self._out), _lib.ptr(self._out_off), None))
         o = self._out_off
         return [self._out[o[s]:o[s + 1]].copy() for s in range(S)]
+
+    def update_streams(self, streams, dets_per_stream, feats_per_stream, warps=None):
+        """update() for the listed stream ids only: every per-stream argument and the result
+        follow `streams` (any order); the other streams of the engine are left exactly as they
+        were (no predict, no ageing, no gallery write, ID counter unchanged)."""
+        ids, order = self._subset(streams, len(dets_per_stream))
+        packed, off, feats, w = self._pack_host(
+            self._reorder(dets_per_stream, order), self._reorder(feats_per_stream, order),
+            self._reorder(warps, order))
+        n = len(ids)
+        o = np.zeros(n + 1, dtype=np.int32)
+        _lib.check(self.lib.yta_strongsort_update_streams(
+            self._h, n, _lib.ptr(ids), _lib.ptr(packed), _lib.ptr(off), _lib.ptr(feats),
+            _lib.ptr(w), _lib.ptr(self._out), len(self._out), _lib.ptr(o), None))
+        return self._subset_result(o, order)
+
+    def update_tensors(self, dets, feats, warps=None, counts=None, active=None, next_id=None,
+                       stream=None):
+        """Stream-ordered update from device tensors to device tensors
+        (yta_strongsort_update_tensors): nothing crosses the link and nothing is waited for.
+        dets: a list of S CUDA tensors (M_s, 6), or one (total, 6) tensor (a column slice of a
+        wider tensor is passed with its row stride) with `counts`, the S per-stream row counts
+        (host ints); float64, float32 or float16, promoted exactly.  feats: one float32
+        feat_dim-wide row per detection row (a list of S (M_s, D) CUDA tensors or one (total, D)
+        tensor, a column slice included), read where they are.  warps: a float64 CUDA tensor of
+        S x 6 values whose NaN rows mean "no camera update for that stream", or a host sequence
+        of S entries, each a 2x3 warp or None (copied on the stream).  active: optional (S,)
+        integer / bool CUDA tensor, nonzero = update that stream; the others keep every byte of
+        their state and report no row.  next_id: optional host int64 (S,) ID counters written
+        before the frame (read next_ids() after a synchronisation).  stream: the torch stream the
+        inputs were produced on and the outputs are consumed on (default: the current one).
+        Returns (rows (total, 8) float64, offsets (S + 1,) int32, row_stream (total,) int32) on
+        the engine's device: stream s's rows are rows[offsets[s]:offsets[s + 1]], row_stream[r] is
+        row r's stream and -1 from offsets[S] on.  Results equal update()'s bit for bit.
+        The engine does not grow: more than max_dets rows for a stream raises CapacityError with
+        nothing enqueued; a stream outgrowing track_capacity is reported by the next sync().
+        Raises ValueError, before anything is enqueued, for tensors on another device or of the
+        wrong shape or dtype."""
+        if warps is not None and not is_cuda_tensor(warps):
+            if len(warps) != self.n_streams:
+                raise ValueError(f"warps: {len(warps)} entries for {self.n_streams} streams")
+            w = np.full((self.n_streams, 6), np.nan)
+            for s, m in enumerate(warps):
+                if m is not None:
+                    w[s] = np.asarray(m, dtype=np.float64).reshape(6)
+            warps = w
+        f = TensorFrame(self, dets, counts, active, next_id, stream, feats=feats, warps=warps)
+        _lib.check(self.lib.yta_strongsort_update_tensors(
+            self._h, *f.common_head(), f._p(f.feats), int(f.feat_stride), f._p(f.warps),
+            *f.common_tail()))
+        return f.result()
 
     def state(self, stream=0):
         """Tracks of one stream in list order: id, hits, age, time_since_update, state (1
@@ -152,7 +222,8 @@ class StrongSORT:
     (or as `reid=`) is used as the feature producer.  Camera motion: ECC on the GPU as in the
     reference (:40 get_cmc_method('ecc')()); `cmc=` replaces it (an object with
     apply(img, dets) -> 2x3).  As in the reference the estimator is called only on frames where
-    the tracker holds a track (:62).
+    the tracker holds a track (:62).  update() also takes a CUDA tensor of detections (and a
+    CUDA frame and embeddings) and then returns a CUDA tensor: see _update_tensor.
     """
 
     def __init__(self, model_weights=None, device=0, fp16=False, max_dist=0.2, max_iou_dist=0.7,
@@ -173,7 +244,86 @@ class StrongSORT:
         if feat_dim is not None:
             self._engine = StrongSortEngine(1, feat_dim=int(feat_dim), **self._kw)
 
+    def _update_tensor(self, dets, img, embs):
+        """update() for a CUDA tensor of detections (embs, when given, a CUDA tensor with one row
+        per detection): the features and the rows stay on the device.  With a CUDA `img` (uint8
+        (h, w, 3), rows any pitch >= 3 * w) nothing crosses the link: the crops and the ECC
+        estimate read the frame and the boxes where they are
+        (ReIDDetectMultiBackend.get_features, ECC.apply) and the warp goes to the engine as a
+        device tensor.  A caller-supplied `reid=` or `cmc=` object that is not this package's gets
+        `img.cpu().numpy()` (one download per call) and NumPy boxes.
+        As in the reference (:62) the estimator runs only on frames entered with >= 1 track, and
+        a skipped frame never becomes ECC's prev_img, so the decision cannot be left to the
+        device: it reads n_tracks(), which waits for the PREVIOUS frame's completion event (page-
+        locked counts, no copy) and never for the frame being enqueued.  That wait is the price of
+        reproducing the reference's skipping; learning K for the returned slice (and whether the
+        frame overran track_capacity) is the other, at the end of the call."""
+        import torch
+        img_dev = is_cuda_tensor(img)
+        assert img_dev or isinstance(img, np.ndarray), \
+            f"Unsupported 'img' input format '{type(img)}', valid format is np.ndarray"
+        assert dets.dim() == 2, "Unsupported 'dets' dimensions, valid number of dimensions is two"
+        assert dets.shape[1] == 6, "Unsupported 'dets' 2nd dimension lenght, valid lenghts is 6"
+        n = dets.shape[0]
+        img_host = None if img_dev else img
+        box_host = None
+
+        def host_img():   # for a foreign reid / cmc object: one download per call
+            nonlocal img_host
+            if img_host is None:
+                img_host = img.cpu().numpy()
+            return img_host
+
+        def host_boxes():
+            nonlocal box_host
+            if box_host is None:
+                box_host = dets[:, 0:4].double().cpu().numpy()
+            return box_host
+
+        warp = None
+        if self._engine is not None and self._engine.n_tracks()[0] >= 1:        # :62-65
+            if img_dev and takes_device_frames(self.cmc):                        # stays in HBM
+                w = self.cmc.apply(img, dets[:, 0:4])
+                warp = w.double().reshape(1, 6) if is_cuda_tensor(w) \
+                    else [np.asarray(w, dtype=np.float64)]
+            else:
+                warp = [np.asarray(self.cmc.apply(host_img(), host_boxes()), dtype=np.float64)]
+        feats = None
+        if n:                                                                    # :68
+            if embs is not None:
+                if not is_cuda_tensor(embs) or embs.dim() != 2 or len(embs) != n:
+                    raise ValueError("embs: with tensor dets, a CUDA tensor with one row per "
+                                     "detection is needed")
+                feats = embs.float()
+            elif self.model is None:
+                raise RuntimeError("StrongSORT needs a ReID producer: pass model weights, an "
+                                   "object with get_features(xyxys, img), or update(dets, img, "
+                                   "embs=...)")
+            elif img_dev and takes_device_frames(self.model):
+                feats = self.model.get_features(dets[:, 0:4], img, as_tensor=True).float()
+            elif "as_tensor" in inspect.signature(self.model.get_features).parameters:
+                feats = self.model.get_features(host_boxes(), host_img(), as_tensor=True).float()
+            else:
+                feats = torch.from_numpy(np.ascontiguousarray(self.model.get_features(
+                    host_boxes(), host_img()), dtype=np.float32)).to(dets.device)
+            feats = feats.reshape(n, -1)
+        if self._engine is None:
+            if feats is None:   # no track, no detection: nothing to remember
+                return dets.new_zeros((0, 8), dtype=torch.float64)
+            self._engine = StrongSortEngine(1, feat_dim=feats.shape[1], **self._kw)
+        if feats is None:
+            feats = torch.zeros((0, self._engine.feat_dim), dtype=torch.float32,
+                                device=dets.device)
+        rows, off, _ = self._engine.update_tensors([dets], [feats], warps=warp)
+        self._engine.sync()   # a track_capacity overrun is raised here, as update() raises it
+        return rows[:int(off[1])]
+
     def update(self, dets, img, embs=None):
+        """dets / img: np.ndarray as the reference; a CUDA tensor (N, 6) of detections is taken
+        where it is (embs then a CUDA tensor too, img a CUDA uint8 tensor or an ndarray) and the
+        (K, 8) result is then a CUDA tensor (empty where the ndarray form returns np.array([]))."""
+        if is_cuda_tensor(dets):
+            return self._update_tensor(dets, img, embs)
         assert isinstance(
             dets, np.ndarray
         ), f"Unsupported 'dets' input format '{type(dets)}', valid format is np.ndarray"
