@@ -1064,6 +1064,27 @@ int yta_osnet_pool(const void *x, int N, int C, int H, int W, int kind, int half
 int yta_osnet_gate(const float *plane_sum, int N, int mid, int hid, int P, const void *w1,
                    const void *b1, const void *w2, const void *b2, int half, void *gate,
                    void *stream);
+/* ---- OSNet-IBN / OSNet-AIN (osnet.py IN=True, osnet_ain.py): nn.InstanceNorm2d(affine=True) in
+ * eval mode, which has no running statistics and cannot be folded into a convolution.
+ * yta_osnet_instnorm: per (sample, channel) plane of P contiguous elements (x, res, y: N x C x P)
+ *   y = relu?( gamma[c] (x - mean) / sqrt(var + 1e-5) + beta[c] + res )
+ * with the plane's own mean and biased variance in float32 (mean first, then the centred sums; no
+ * E[x^2] - mean^2), summed in a fixed order without atomics: the same input gives the same bits.
+ * res may be NULL (AIN's identity sits outside the norm, IBN's inside: it passes the summed tensor
+ * and no res); y must not alias x.  A plane of up to yta_osnet_instnorm_resident() elements is
+ * read from memory once; larger planes are read three times.
+ * yta_osnet_instnorm_maxpool: the stem of both variants, max_pool2d(relu(instance norm(x)), 3, 2,
+ * 1): x N x C x H x W -> y N x C x ((H-1)/2+1) x ((W-1)/2+1), the normalised plane never written.
+ * work: N x C x H x W elements of scratch, read only when H W exceeds the resident bound (NULL
+ * otherwise): such planes go through yta_osnet_instnorm and yta_osnet_pool.
+ * yta_osnet_stem_linear: yta_osnet_stem without the ReLU (the clamp belongs after the norm). */
+int yta_osnet_instnorm_resident(void);
+int yta_osnet_instnorm(const void *x, const void *res, const float *gamma, const float *beta,
+                       int N, int C, int P, int relu, int half, void *y, void *stream);
+int yta_osnet_instnorm_maxpool(const void *x, const float *gamma, const float *beta, int N, int C,
+                               int H, int W, int half, void *work, void *y, void *stream);
+int yta_osnet_stem_linear(const void *x, int N, int H, int W, const float *w, const float *b,
+                          int C0, int half, void *y, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 """ReID producer end to end on the MI355X: crops of S camera streams x M
 detections (1920x1080 BGR, one yta_reid_preprocess_device launch) + the OSNet forward
 (appearance/osnet.py: folded BatchNorms, channels-last, batched branches; random weights of the
-named variant) + global normalisation, features left on the device.  Reports crops/s for the
+named variant, any key of appearance/osnet.py VARIANTS: the plain widths, osnet_ibn_* and
+osnet_ain_* with their instance norms) + global normalisation, features left on the device.  Reports crops/s for the
 network alone and for the whole get_features path, float32 and float16.  Prints JSON lines."""
 import argparse
 import json
@@ -17,7 +18,9 @@ sys.path.insert(0, REPO)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variant", default="osnet_x0_25")
+    from yolo_tracking_amd.appearance.osnet import VARIANTS
+    ap.add_argument("--variant", default="osnet_x0_25", choices=sorted(VARIANTS),
+                    help="OSNet variant: plain, osnet_ibn_* or osnet_ain_* (default osnet_x0_25)")
     ap.add_argument("--crops", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=10)
     args = ap.parse_args()

@@ -282,6 +282,10 @@ _SIGS = {
     "yta_osnet_stem": ([_P, _I, _I, _I, _P, _P, _I, _I, _P, _P], _I),
     "yta_osnet_pool": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
     "yta_osnet_gate": ([_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P], _I),
+    "yta_osnet_instnorm_resident": ([], _I),
+    "yta_osnet_instnorm": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P], _I),
+    "yta_osnet_instnorm_maxpool": ([_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P], _I),
+    "yta_osnet_stem_linear": ([_P, _I, _I, _I, _P, _P, _I, _I, _P, _P], _I),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

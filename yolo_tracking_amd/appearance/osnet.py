@@ -13,6 +13,15 @@ gate over all four branches at once.  Parameters are taken from a checkpoint in 
 key layout (torchreid's names: conv1.conv.weight, conv2.0.conv2b.1.bn.running_var, ...), so the
 reference's .pt weight files load unchanged; parity with the reference network is pinned by
 tests/golden/osnet_x0_25.npz (the reference module with random weights, eval mode).
+
+OSNet-IBN (osnet.py with IN=True: osnet_ibn_x1_0) and OSNet-AIN (backbones/osnet_ain.py:
+osnet_ain_x1_0 .. x0_25) are the same graph plus nn.InstanceNorm2d(affine=True), which in eval
+mode still normalises every (crop, channel) plane by that plane's own statistics and so cannot be
+folded: after the stem convolution (conv -> IN -> ReLU -> max pool) and at the end of a block,
+either around the residual sum (IBN, stage conv2 only: relu(IN(conv3(x2) + identity))) or inside
+it (AIN's OSBlockINin: relu(IN(conv3(x2)) + identity), conv3 without BatchNorm).  AIN names its
+branches conv2.{t}.layers.{d} and its transitions pool2.0 / pool3.0; parity is pinned by
+tests/golden/osnet_ain_x0_25.npz and osnet_ibn_x0_25.npz.
 """
 import math
 import re
@@ -21,24 +30,43 @@ import numpy as np
 
 WIDTHS = {"osnet_x1_0": (64, 256, 384, 512), "osnet_x0_75": (48, 192, 288, 384),
           "osnet_x0_5": (32, 128, 192, 256), "osnet_x0_25": (16, 64, 96, 128)}
+# name -> (widths, kind): plain (osnet.py), ibn (osnet.py IN=True: instance norm after the stem
+# convolution and at the end of the two conv2 blocks), ain (osnet_ain.py: the same stem, blocks
+# per stage as AIN_BLOCKS, 'in' = OSBlockINin).  The reference registers osnet_ibn_x1_0 only; the
+# narrower IBN widths are the same class with other channel counts.
+VARIANTS = {name: (w, "plain") for name, w in WIDTHS.items()}
+VARIANTS.update({name.replace("osnet_", "osnet_ibn_"): (w, "ibn") for name, w in WIDTHS.items()})
+VARIANTS.update({name.replace("osnet_", "osnet_ain_"): (w, "ain") for name, w in WIDTHS.items()})
+AIN_BLOCKS = (("in", "in"), ("os", "in"), ("in", "os"))
 FEATURE_DIM = 512
 BN_EPS = 1e-5
+IN_EPS = 1e-5   # nn.InstanceNorm2d's default
 CHUNK = 1024   # crops per forward pass: bounds the activations (the block's tensors stay in cache)
 
 
 def model_name(weights):
     """The OSNet variant a weight file name names (reid_model_factory.get_model_name)."""
     s = str(weights)
-    for name in sorted(WIDTHS, key=len, reverse=True):
+    for name in sorted(VARIANTS, key=len, reverse=True):
         if name in s:
             return name
     return None
 
 
+def _block_norms(kind, stage):
+    """The instance norm of the two blocks of stage 0..2 (conv2..conv4): None, 'ibn' or 'in'."""
+    if kind == "ibn":
+        return ("ibn", "ibn") if stage == 0 else (None, None)
+    if kind == "ain":
+        return tuple("in" if b == "in" else None for b in AIN_BLOCKS[stage])
+    return (None, None)
+
+
 def random_state_dict(name="osnet_x0_25", seed=0):
     """A state_dict in the reference's key layout with freshly initialised weights (kaiming
-    normal fan-out for convolutions, N(0, 0.01) for the fc, identity BatchNorms): what the
-    reference's constructor gives without pretrained weights."""
+    normal fan-out for convolutions, N(0, 0.01) for the fc, identity BatchNorms and instance
+    norms, the latter without running statistics): what the reference's constructor gives without
+    pretrained weights, in the key layout of the variant's class (osnet.py / osnet_ain.py)."""
     rng = np.random.default_rng(seed)
     sd = {}
 
@@ -54,39 +82,57 @@ def random_state_dict(name="osnet_x0_25", seed=0):
         sd[key + ".running_mean"] = np.zeros(c, np.float32)
         sd[key + ".running_var"] = np.ones(c, np.float32)
 
+    def inorm(key, c):
+        sd[key + ".weight"] = np.ones(c, np.float32)
+        sd[key + ".bias"] = np.zeros(c, np.float32)
+
     def light(key, c):
         conv(key + ".conv1", c, c, 1)
         std = math.sqrt(2.0 / (c * 9))
         sd[key + ".conv2.weight"] = rng.normal(0, std, (c, 1, 3, 3)).astype(np.float32)
         bn(key + ".bn", c)
 
-    def block(key, cin, cout):
+    def block(key, cin, cout, norm=None):
+        """norm: None, 'ibn' (OSBlock(IN=True)) or 'in' (OSBlockINin: conv3 without BatchNorm)."""
         mid = cout // 4
         conv(key + ".conv1.conv", mid, cin, 1)
         bn(key + ".conv1.bn", mid)
-        light(key + ".conv2a", mid)
-        for br, depth in (("conv2b", 2), ("conv2c", 3), ("conv2d", 4)):
-            for d in range(depth):
-                light(f"{key}.{br}.{d}", mid)
+        if kind == "ain":
+            for t in range(4):
+                for d in range(t + 1):
+                    light(f"{key}.conv2.{t}.layers.{d}", mid)
+        else:
+            light(key + ".conv2a", mid)
+            for br, depth in (("conv2b", 2), ("conv2c", 3), ("conv2d", 4)):
+                for d in range(depth):
+                    light(f"{key}.{br}.{d}", mid)
         conv(key + ".gate.fc1", mid // 16, mid, 1, bias=True)
         conv(key + ".gate.fc2", mid, mid // 16, 1, bias=True)
         conv(key + ".conv3.conv", cout, mid, 1)
-        bn(key + ".conv3.bn", cout)
+        if norm != "in":
+            bn(key + ".conv3.bn", cout)
         if cin != cout:
             conv(key + ".downsample.conv", cout, cin, 1)
             bn(key + ".downsample.bn", cout)
+        if norm:
+            inorm(key + ".IN", cout)
 
-    c = WIDTHS[name]
+    c, kind = VARIANTS[name]
     conv("conv1.conv", c[0], 3, 7)
-    bn("conv1.bn", c[0])
+    if kind == "plain":
+        bn("conv1.bn", c[0])
+    else:
+        inorm("conv1.bn", c[0])
     for stage, (cin, cout, reduce) in enumerate(((c[0], c[1], True), (c[1], c[2], True),
                                                  (c[2], c[3], False))):
         key = f"conv{stage + 2}"
-        block(key + ".0", cin, cout)
-        block(key + ".1", cout, cout)
+        norms = _block_norms(kind, stage)
+        block(key + ".0", cin, cout, norms[0])
+        block(key + ".1", cout, cout, norms[1])
         if reduce:
-            conv(key + ".2.0.conv", cout, cout, 1)
-            bn(key + ".2.0.bn", cout)
+            red = f"pool{stage + 2}.0" if kind == "ain" else key + ".2.0"
+            conv(red + ".conv", cout, cout, 1)
+            bn(red + ".bn", cout)
     conv("conv5.conv", c[3], c[3], 1)
     bn("conv5.bn", c[3])
     sd["fc.0.weight"] = rng.normal(0, 0.01, (FEATURE_DIM, c[3])).astype(np.float32)
@@ -112,19 +158,20 @@ class OSNetReID:
 
     On a GPU every layer runs in csrc/osnet.hip (NCHW): the stem (7x7 conv), the pools, every
     1x1 convolution and the fc as MFMA GEMMs with bias / residual / ReLU epilogues, the depthwise
-    3x3s, the channel gates and the gated branch sums; PyTorch only allocates the activations.
+    3x3s, the channel gates, the gated branch sums and (osnet_ibn_* / osnet_ain_*) the instance
+    norms; PyTorch only allocates the activations.
     `hip=False` runs the same folded graph on PyTorch's kernels (MIOpen), for comparison, and is
     what a CPU device gets."""
 
     def __init__(self, name="osnet_x0_25", state_dict=None, device="cuda:0", half=False,
                  chunk=CHUNK, channels_last=None, hip=True):
         import torch
-        if name not in WIDTHS:
+        if name not in VARIANTS:
             raise KeyError(f"unknown OSNet variant {name!r}")
         self.torch = torch
         self.chunk = int(chunk)
         self.name = name
-        self.widths = WIDTHS[name]
+        self.widths, self.kind = VARIANTS[name]
         self.device = torch.device(device)
         self.hip = bool(hip) and self.device.type == "cuda"
         if channels_last is None:
@@ -158,14 +205,19 @@ class OSNetReID:
 
     def _build(self, sd):
         P = {}
-        w, b = self._fold(sd["conv1.conv.weight"], sd, "conv1.bn")
-        P["stem"] = (self._t(w), self._t(b))
+        if self.kind == "plain":
+            w, b = self._fold(sd["conv1.conv.weight"], sd, "conv1.bn")
+            P["stem"] = (self._t(w), self._t(b))
+        else:   # conv -> instance norm -> ReLU: conv1.bn is the norm's affine pair, nothing folds
+            w, b = sd["conv1.conv.weight"], self.torch.zeros_like(sd["conv1.bn.bias"])
+            P["stem"] = (self._t(w), None)
+            P["stem_norm"] = self._norm(sd, "conv1.bn")
         H = {"stem": (self._f32(w), self._f32(b))}      # the HIP kernels' float32 operands
         self.blocks = []
         for stage in (2, 3, 4):
-            for i in (0, 1):
-                self.blocks.append(self._block(sd, f"conv{stage}.{i}"))
-            red = f"conv{stage}.2.0"
+            for i, norm in enumerate(_block_norms(self.kind, stage - 2)):
+                self.blocks.append(self._block(sd, f"conv{stage}.{i}", norm))
+            red = f"pool{stage}.0" if self.kind == "ain" else f"conv{stage}.2.0"
             if red + ".conv.weight" in sd:
                 w, b = self._fold(sd[red + ".conv.weight"], sd, red + ".bn")
                 self.blocks.append(("reduce", self._t(w), self._t(b),
@@ -180,13 +232,24 @@ class OSNetReID:
         self.P = P
         self.H = H
 
-    def _block(self, sd, key):
+    def _norm(self, sd, key):
+        """An instance norm's affine pair: (gamma, beta) for PyTorch's operator in the storage
+        type, then as the float32 operands of yta_osnet_instnorm."""
+        g, b = sd[key + ".weight"], sd[key + ".bias"]
+        return (self._t(g), self._t(b), self._f32(g), self._f32(b))
+
+    def _block(self, sd, key, norm=None):
+        """norm: None (OSBlock), 'ibn' (OSBlock(IN=True): the norm around conv3 + identity) or
+        'in' (OSBlockINin: the norm on conv3 alone, which has no BatchNorm, inside the residual)."""
         torch = self.torch
         w1, b1 = self._fold(sd[key + ".conv1.conv.weight"], sd, key + ".conv1.bn")
         mid = w1.shape[0]
-        branches = [[key + ".conv2a"]] + [[f"{key}.{br}.{d}" for d in range(depth)]
-                                          for br, depth in (("conv2b", 2), ("conv2c", 3),
-                                                            ("conv2d", 4))]
+        if self.kind == "ain":
+            branches = [[f"{key}.conv2.{t}.layers.{d}" for d in range(t + 1)] for t in range(4)]
+        else:
+            branches = [[key + ".conv2a"]] + [[f"{key}.{br}.{d}" for d in range(depth)]
+                                              for br, depth in (("conv2b", 2), ("conv2c", 3),
+                                                                ("conv2d", 4))]
         layers = []   # depth d: the branches still running, 1x1 weights stacked, dw folded
         pw32 = []     # the same 1x1 weights as the HIP GEMM's float32 [groups][cout_g][k]
         for d in range(4):
@@ -202,27 +265,35 @@ class OSNetReID:
              self._t(sd[key + ".gate.fc1.bias"]),
              self._t(sd[key + ".gate.fc2.weight"].reshape(mid, -1)),
              self._t(sd[key + ".gate.fc2.bias"]))
-        w3, b3 = self._fold(sd[key + ".conv3.conv.weight"], sd, key + ".conv3.bn")
+        if norm == "in":
+            w3, b3 = sd[key + ".conv3.conv.weight"], None
+        else:
+            w3, b3 = self._fold(sd[key + ".conv3.conv.weight"], sd, key + ".conv3.bn")
         ds = None
         cout, cin = w3.shape[0], w1.shape[1]
         w3k, b3k = w3.reshape(cout, mid), b3
+        hip = {"conv1": (self._f32(w1, (1, mid, cin)), self._f32(b1)),
+               "layers": pw32, "cin": cin, "cout": cout, "hid": g[0].shape[0], "norm": norm}
         if key + ".downsample.conv.weight" in sd:
             wd, bd = self._fold(sd[key + ".downsample.conv.weight"], sd, key + ".downsample.bn")
             ds = (self._t(wd), self._t(bd))
-            # conv3(x2) + downsample(x): one GEMM over the concatenated inputs [x2; x]
-            w3k, b3k = torch.cat([w3k, wd.reshape(cout, cin)], 1), b3 + bd
-        hip = {"conv1": (self._f32(w1, (1, mid, cin)), self._f32(b1)),
-               "layers": pw32,
-               "conv3": (self._f32(w3k, (1,) + tuple(w3k.shape)), self._f32(b3k)),
-               "cin": cin, "cout": cout, "hid": g[0].shape[0]}
-        return ("os", mid, (self._t(w1), self._t(b1)), layers, g, (self._t(w3), self._t(b3)), ds,
-                hip)
+            if norm == "in":   # the norm stands between conv3 and the sum: a GEMM of its own
+                hip["ds"] = (self._f32(wd, (1, cout, cin)), self._f32(bd))
+            else:
+                # conv3(x2) + downsample(x): one GEMM over the concatenated inputs [x2; x]
+                w3k, b3k = torch.cat([w3k, wd.reshape(cout, cin)], 1), b3 + bd
+        hip["conv3"] = (self._f32(w3k, (1,) + tuple(w3k.shape)),
+                        self._f32(b3k) if b3k is not None else None)
+        if norm:
+            hip["in"] = self._norm(sd, key + ".IN")
+        return ("os", mid, (self._t(w1), self._t(b1)), layers, g,
+                (self._t(w3), self._t(b3) if b3 is not None else None), ds, hip)
 
     # ---- forward
     def _os_block(self, x, blk):
         F = self.torch.nn.functional
         torch = self.torch
-        _, mid, (w1, b1), layers, (g1w, g1b, g2w, g2b), (w3, b3), ds, _ = blk
+        _, mid, (w1, b1), layers, (g1w, g1b, g2w, g2b), (w3, b3), ds, hp = blk
         x1 = F.relu(F.conv2d(x, w1, b1))
         outs = []                       # branch outputs, finished at depths 1, 2, 3, 4
         y = None
@@ -241,7 +312,12 @@ class OSNetReID:
         x2 = x2.contiguous(memory_format=self.fmt)
         x3 = F.conv2d(x2, w3, b3)
         idt = F.conv2d(x, ds[0], ds[1]) if ds is not None else x
-        return F.relu(x3 + idt)
+        if hp["norm"] == "in":
+            x3 = F.instance_norm(x3, weight=hp["in"][0], bias=hp["in"][1], eps=IN_EPS)
+        out = x3 + idt
+        if hp["norm"] == "ibn":
+            out = F.instance_norm(out, weight=hp["in"][0], bias=hp["in"][1], eps=IN_EPS)
+        return F.relu(out)
 
     # ---- the HIP forward (csrc/osnet.hip): every layer a kernel of ours
     def _pw(self, x1, w, bias=None, *, k1, G=1, cout_g, P, N, relu, x2=None, k2=0, res=None,
@@ -278,7 +354,9 @@ class OSNetReID:
         by branch after depth 0) and the depthwise 3x3 + bias + ReLU, which routes the branch
         ending at that depth into the (N, 4, mid, H, W) stack with its plane sums; the channel gate
         on those sums; the gated branch sum; conv3 and the downsample 1x1 as one GEMM over [x2; x]
-        (or + x) with ReLU."""
+        (or + x) with ReLU.  With an instance norm the GEMM leaves the ReLU to yta_osnet_instnorm:
+        IBN normalises that sum; an OSBlockINin normalises conv3 alone and adds the identity (x,
+        or the downsample as a GEMM of its own) as the norm's residual."""
         ctypes = self._ctypes
         from .. import _lib
         torch = self.torch
@@ -317,11 +395,33 @@ class OSNetReID:
                                           ctypes.c_void_p(x2.data_ptr()), st))
         w3, b3 = hp["conv3"]
         cout = hp["cout"]
-        if ds is not None:
-            out = self._pw(x2, w3, b3, k1=mid, cout_g=cout, P=hw, N=n, relu=True, x2=x, k2=cin)
+        norm = hp["norm"]
+        if norm == "in":
+            y3 = self._pw(x2, w3, None, k1=mid, cout_g=cout, P=hw, N=n, relu=False)
+            idt = (self._pw(x, *hp["ds"], k1=cin, cout_g=cout, P=hw, N=n, relu=False)
+                   if ds is not None else x)
+            out = self._instnorm(y3, hp["in"], n, cout, hw, res=idt)
         else:
-            out = self._pw(x2, w3, b3, k1=mid, cout_g=cout, P=hw, N=n, relu=True, res=x)
+            if ds is not None:
+                out = self._pw(x2, w3, b3, k1=mid, cout_g=cout, P=hw, N=n, relu=not norm, x2=x,
+                               k2=cin)
+            else:
+                out = self._pw(x2, w3, b3, k1=mid, cout_g=cout, P=hw, N=n, relu=not norm, res=x)
+            if norm:
+                out = self._instnorm(out, hp["in"], n, cout, hw)
         return out.view(n, cout, h, w)
+
+    def _instnorm(self, x, pair, n, c, p, res=None):
+        """relu(instance norm(x) + res) through yta_osnet_instnorm (x, res: n x c x p)."""
+        from .. import _lib
+        ctypes = self._ctypes
+        out = self.torch.empty((n, c, p), dtype=self.dtype, device=self.device)
+        _lib.check(_lib.load_library().yta_osnet_instnorm(
+            ctypes.c_void_p(x.data_ptr()),
+            ctypes.c_void_p(res.data_ptr()) if res is not None else None,
+            ctypes.c_void_p(pair[2].data_ptr()), ctypes.c_void_p(pair[3].data_ptr()), n, c, p, 1,
+            self._half, ctypes.c_void_p(out.data_ptr()), self._stream()))
+        return out
 
     def _pool(self, x, kind):
         from .. import _lib
@@ -351,11 +451,25 @@ class OSNetReID:
         c0 = ws.shape[0]
         stem = torch.empty((n, c0, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=self.dtype,
                            device=self.device)
-        _lib.check(_lib.load_library().yta_osnet_stem(
+        lib = _lib.load_library()
+        conv = lib.yta_osnet_stem if self.kind == "plain" else lib.yta_osnet_stem_linear
+        _lib.check(conv(
             ctypes.c_void_p(x.data_ptr()), n, H, W, ctypes.c_void_p(ws.data_ptr()),
             ctypes.c_void_p(bs.data_ptr()), c0, self._half, ctypes.c_void_p(stem.data_ptr()),
             self._stream()))
-        x = self._pool(stem, 0)
+        if self.kind == "plain":
+            x = self._pool(stem, 0)
+        else:   # instance norm + ReLU + max pool in one pass over the stem's planes
+            sh, sw = stem.shape[2], stem.shape[3]
+            pair = self.P["stem_norm"]
+            work = torch.empty_like(stem) if sh * sw > lib.yta_osnet_instnorm_resident() else None
+            x = torch.empty((n, c0, (sh - 1) // 2 + 1, (sw - 1) // 2 + 1), dtype=self.dtype,
+                            device=self.device)
+            _lib.check(lib.yta_osnet_instnorm_maxpool(
+                ctypes.c_void_p(stem.data_ptr()), ctypes.c_void_p(pair[2].data_ptr()),
+                ctypes.c_void_p(pair[3].data_ptr()), n, c0, sh, sw, self._half,
+                ctypes.c_void_p(work.data_ptr()) if work is not None else None,
+                ctypes.c_void_p(x.data_ptr()), self._stream()))
         for blk in self.blocks:
             if blk[0] == "reduce":
                 _, _, _, wr, br = blk
@@ -391,8 +505,11 @@ class OSNetReID:
         F = torch.nn.functional
         x = crops.to(self.device, self.dtype).contiguous(memory_format=self.fmt)
         w, b = self.P["stem"]
-        x = F.relu(F.conv2d(x, w, b, stride=2, padding=3))
-        x = F.max_pool2d(x, 3, stride=2, padding=1)
+        x = F.conv2d(x, w, b, stride=2, padding=3)
+        if self.kind != "plain":
+            g, bt = self.P["stem_norm"][:2]
+            x = F.instance_norm(x, weight=g, bias=bt, eps=IN_EPS)
+        x = F.max_pool2d(F.relu(x), 3, stride=2, padding=1)
         for blk in self.blocks:
             if blk[0] == "reduce":
                 x = F.avg_pool2d(F.relu(F.conv2d(x, blk[1], blk[2])), 2, stride=2)

@@ -13,7 +13,9 @@ then a zero crop instead of an error.
 
 The network: OSNet (appearance/osnet.py, an eval-mode inference graph with folded BatchNorms,
 channels-last, batched branches) built from `weights` as the reference builds it from the weight
-file name (reid_multibackend.py:57-80, osnet_x0_25 .. osnet_x1_0); the reference's .pt state dicts
+file name (reid_multibackend.py:57-80): osnet_x0_25 .. osnet_x1_0, and the instance-norm members
+of the family, osnet_ibn_x1_0 and osnet_ain_x1_0 (and their narrower widths), whose norms run in
+csrc/osnet.hip as well; the reference's .pt state dicts
 load unchanged (torch.load(weights_only=True)).  A weight file that is not on disk would be
 downloaded by the reference (gdown, :61-64) or end the program (:67-72); there is no network here,
 so a missing file raises FileNotFoundError.  Freshly initialised weights (benchmarks, plumbing
@@ -101,13 +103,15 @@ class ReIDDetectMultiBackend:
         self.model = model
 
     def _build_osnet(self, weights):
-        """reid_multibackend.py:57-80 for the OSNet family (the trackers' default weights)."""
+        """reid_multibackend.py:57-80 for the OSNet family: the plain widths (the trackers'
+        default weights), osnet_ibn_* and osnet_ain_* (appearance/osnet.py VARIANTS)."""
         from .osnet import OSNetReID, load_checkpoint, model_name
         name = model_name(weights)
         if name is None:
             raise NotImplementedError(
-                f"ReID weights {str(weights)!r}: only the OSNet family (osnet_x0_25 .. osnet_x1_0) "
-                "is rebuilt on the MI355X path; pass model=<torch module> for other networks")
+                f"ReID weights {str(weights)!r}: only the OSNet family (osnet_x0_25 .. osnet_x1_0, "
+                "osnet_ibn_x1_0, osnet_ain_x1_0 and their other widths) is rebuilt on the MI355X "
+                "path; pass model=<torch module> for other networks")
         w = Path(weights)
         if w.is_file():
             sd = load_checkpoint(w)

@@ -20,7 +20,11 @@
 //              16 output channels per pass in registers, weights broadcast from LDS;
 //   k_pool     max 3x3 stride 2 pad 1 / average 2x2 stride 2 / global mean (OSNet's pools);
 //   k_gate     ChannelGate's two 1x1 layers on the pooled branch planes (fc1 + ReLU, fc2 +
-//              sigmoid), one block per sample.
+//              sigmoid), one block per sample;
+//   k_instnorm the instance norm of OSNet-IBN / OSNet-AIN (osnet_ain.py OSBlockINin): per-plane
+//              statistics in two fixed-order passes over a plane held in LDS, affine, residual and
+//              ReLU fused, or (the stem) + ReLU + the 3x3 max pool with only the pooled plane
+//              written; k_instnorm_loop for planes that do not fit.
 // NCHW planes, float32 or float16 storage, float32 arithmetic.
 #include <algorithm>
 
@@ -244,9 +248,10 @@ __global__ __launch_bounds__(PW_T) void k_pw(yta_pw_args a) {
 // computes a 16 x 16 tile of output pixels; the input tile (3 x 37 x 37 with the halo) sits in
 // LDS, each thread keeps the C0 (a multiple of 16, <= 64 per pass) accumulators of its pixel in
 // registers and reads every input value once per pass, the weights being uniform across the block
-// (scalar loads).
+// (scalar loads).  RELU = false: the convolution alone, for the variants whose stem is followed by
+// an instance norm (the clamp belongs after the norm there).
 constexpr int ST_TILE = 16, ST_IN = 2 * ST_TILE + 5;   // 37 input rows / columns per tile
-template <typename T, int CB>
+template <typename T, int CB, bool RELU>
 __global__ __launch_bounds__(256) void k_stem(const T *x, int H, int W, const float *w,
                                               const float *b, int C0, T *y, int Ho, int Wo) {
     __shared__ float tile[3][ST_IN][ST_IN + 1];
@@ -295,7 +300,8 @@ __global__ __launch_bounds__(256) void k_stem(const T *x, int H, int W, const fl
         if (on)
 #pragma unroll
             for (int q = 0; q < CB; ++q)
-                y[(((long long)n * C0 + cb + q) * Ho + oy) * Wo + ox] = (T)fmaxf(acc[q], 0.f);
+                y[(((long long)n * C0 + cb + q) * Ho + oy) * Wo + ox] =
+                    (T)(RELU ? fmaxf(acc[q], 0.f) : acc[q]);
     }
 }
 
@@ -345,6 +351,224 @@ __global__ __launch_bounds__(256) void k_pool(const T *x, int C, int H, int W, i
     }
 }
 
+// ------------------------------------------------------------------------------------ k_instnorm
+// nn.InstanceNorm2d(affine=True) in eval mode (osnet.py ConvLayer(IN=True) / OSBlock.IN,
+// osnet_ain.py OSBlockINin.IN): no running statistics, so every (sample, channel) plane is
+// normalised by its own mean and biased variance (eps 1e-5), then gamma[c] x_hat + beta[c], with
+// the AIN residual and the ReLU fused.  The statistics cannot be folded into a convolution and are
+// not accumulated across blocks: GS threads own a plane (16 or 64 lanes of a wave for the small
+// late-stage planes, so a block takes 16 or 4 of them; the whole block up to IN_RESIDENT_PX
+// pixels), read it from HBM once into LDS as float32 (16-byte loads where the planes are aligned)
+// and make both statistic passes and the write from there.  Two passes, no E[x^2] - mean^2: the
+// mean m0 first (clamped into the plane's [min, max], which makes a constant plane exact), then
+// s1 = sum(x - m0) and s2 = sum((x - m0)^2) together; s1 / P corrects the float32 mean to first
+// order and var = s2 / P - (s1 / P)^2.  Every sum runs in a fixed order (a thread's strided
+// elements, xor butterflies inside the wave, the four waves' partials in wave order), without
+// atomics: the same input gives the same bits.
+constexpr int IN_T = 256;
+constexpr int IN_RESIDENT_PX = 8192;   // 32 KiB of LDS: the x1_0 stem plane at 256 x 128 crops
+constexpr float IN_EPS = 1e-5f;
+enum { IN_SUM = 0, IN_MIN = 1, IN_MAX = 2 };
+
+template <typename T, int V>
+struct alignas(sizeof(T) * V) in_vec { T v[V]; };
+
+template <int OP>
+__device__ __forceinline__ float in_op(float a, float b) {
+    return OP == IN_SUM ? a + b : (OP == IN_MIN ? fminf(a, b) : fmaxf(a, b));
+}
+
+// Over the GS lanes of a wave that own a plane (the whole wave for GS = 256): every lane gets the
+// same value.
+template <int GS, int OP>
+__device__ __forceinline__ float in_lanes(float v) {
+#pragma unroll
+    for (int m = 1; m < (GS < WAVE ? GS : WAVE); m <<= 1) v = in_op<OP>(v, __shfl_xor(v, m, WAVE));
+    return v;
+}
+
+// The statistics of the plane `get(i)`, i < P, for the GS threads that own it (t: the thread's
+// index among them); red: 5 x 4 floats of LDS for the block-wide case.  Block-uniform control
+// flow (a group without a plane passes live = false and still meets the barriers); the first
+// barrier also publishes what `get` left in LDS during the first pass.
+template <int GS, typename Get1, typename Get2>
+__device__ __forceinline__ void in_stats(int P, int t, bool live, float (*red)[IN_T / WAVE],
+                                         Get1 first_pass, Get2 get, float *mean0, float *dmean,
+                                         float *inv_std) {
+    const int wv = threadIdx.x / WAVE;
+    float s = 0.f, lo = INFINITY, hi = -INFINITY;
+    if (live) first_pass(s, lo, hi);
+    s = in_lanes<GS, IN_SUM>(s);
+    lo = in_lanes<GS, IN_MIN>(lo);
+    hi = in_lanes<GS, IN_MAX>(hi);
+    if (GS == IN_T && lane_id() == 0) { red[0][wv] = s; red[1][wv] = lo; red[2][wv] = hi; }
+    __syncthreads();
+    if (GS == IN_T) {
+        s = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+        lo = fminf(fminf(red[1][0], red[1][1]), fminf(red[1][2], red[1][3]));
+        hi = fmaxf(fmaxf(red[2][0], red[2][1]), fmaxf(red[2][2], red[2][3]));
+    }
+    const float m0 = fminf(fmaxf(s / (float)P, lo), hi);
+    float s1 = 0.f, s2 = 0.f;
+    if (live)
+        for (int i = t; i < P; i += GS) {
+            const float d = get(i) - m0;
+            s1 += d;
+            s2 += d * d;
+        }
+    s1 = in_lanes<GS, IN_SUM>(s1);
+    s2 = in_lanes<GS, IN_SUM>(s2);
+    if (GS == IN_T) {
+        if (lane_id() == 0) { red[3][wv] = s1; red[4][wv] = s2; }
+        __syncthreads();
+        s1 = ((red[3][0] + red[3][1]) + red[3][2]) + red[3][3];
+        s2 = ((red[4][0] + red[4][1]) + red[4][2]) + red[4][3];
+    }
+    const float dm = s1 / (float)P;
+    const float var = fmaxf(s2 / (float)P - dm * dm, 0.f);
+    *mean0 = m0;
+    *dmean = dm;
+    *inv_std = 1.0f / sqrtf(var + IN_EPS);
+}
+
+// Resident planes (P <= IN_RESIDENT_PX): block b owns planes b * (IN_T / GS) ... of the N * C,
+// each in its own (P rounded up to 4) floats of dynamic LDS.  POOL: only max_pool2d(3, 2, 1) of
+// the normalised plane + ReLU is written, straight from the plane in LDS (the stem: the network's
+// largest activation is neither written nor read back).
+template <typename T, int GS, bool POOL>
+__global__ __launch_bounds__(IN_T) void k_instnorm(const T *x, const T *res, const float *gamma,
+                                                   const float *beta, long long planes, int C,
+                                                   int P, int vec, int relu, T *y, int H, int W,
+                                                   int Ho, int Wo) {
+    extern __shared__ __attribute__((aligned(16))) float in_lds[];
+    __shared__ float red[5][IN_T / WAVE];
+    constexpr int V = 16 / sizeof(T);
+    const int g = threadIdx.x / GS, t = threadIdx.x - g * GS;
+    const long long pl = (long long)blockIdx.x * (IN_T / GS) + g;
+    const bool live = pl < planes;
+    float *buf = in_lds + g * ((P + 3) & ~3);
+    const T *src = x + pl * P;
+    float m0, dm, inv;
+    in_stats<GS>(
+        P, t, live, red,
+        [&](float &s, float &lo, float &hi) {
+            if (vec) {
+#pragma unroll 4
+                for (int i = t * V; i < P; i += GS * V) {
+                    const in_vec<T, V> q = *reinterpret_cast<const in_vec<T, V> *>(src + i);
+                    float f[V];
+#pragma unroll
+                    for (int u = 0; u < V; ++u) {
+                        f[u] = (float)q.v[u];
+                        s += f[u];
+                        lo = fminf(lo, f[u]);
+                        hi = fmaxf(hi, f[u]);
+                    }
+#pragma unroll
+                    for (int u = 0; u < V; u += 4)
+                        *reinterpret_cast<float4 *>(buf + i + u) =
+                            make_float4(f[u], f[u + 1], f[u + 2], f[u + 3]);
+                }
+            } else {
+                for (int i = t; i < P; i += GS) {
+                    const float f = (float)src[i];
+                    buf[i] = f;
+                    s += f;
+                    lo = fminf(lo, f);
+                    hi = fmaxf(hi, f);
+                }
+            }
+        },
+        [&](int i) { return buf[i]; }, &m0, &dm, &inv);
+    const int c = (int)(pl % C);
+    const float sc = live ? gamma[c] * inv : 0.f, bt = live ? beta[c] : 0.f;
+    if (POOL) {
+        // f(x) = relu(((x - m0) - dm) * sc + bt) is monotone in x, every rounding included (rising
+        // for sc >= 0, falling for a negative gamma), so the window's maximum of f is f of the
+        // window's largest (smallest) input: one affine step per output, and the plane in LDS is
+        // only read.  Taps outside the plane are clamped onto it: a repeated tap changes neither
+        // maximum nor minimum.
+        if (!live) return;
+        T *dst = y + pl * Ho * Wo;
+        const float invWo = 1.0f / (float)Wo;   // i / Wo for i < 2^22, as in k_dw3x3_lds
+        for (int i = t; i < Ho * Wo; i += GS) {
+            const int oy = (int)(((float)i + 0.5f) * invWo), ox = i - oy * Wo;
+            const int x1 = 2 * ox, x0 = x1 > 0 ? x1 - 1 : 0, x2 = x1 + 1 < W ? x1 + 1 : W - 1;
+            const float *r1 = buf + 2 * oy * W, *r0 = oy > 0 ? r1 - W : r1,
+                        *r2 = 2 * oy + 1 < H ? r1 + W : r1;
+            const float a[9] = {r0[x0], r0[x1], r0[x2], r1[x0], r1[x1], r1[x2],
+                                r2[x0], r2[x1], r2[x2]};
+            float mx = a[0], mn = a[0];
+#pragma unroll
+            for (int u = 1; u < 9; ++u) {
+                mx = fmaxf(mx, a[u]);
+                mn = fminf(mn, a[u]);
+            }
+            dst[i] = (T)fmaxf((((sc >= 0.f ? mx : mn) - m0) - dm) * sc + bt, 0.f);
+        }
+        return;
+    }
+    if (!live) return;
+    T *dst = y + pl * P;
+    const T *rs = res ? res + pl * P : nullptr;
+    if (vec) {
+#pragma unroll 2
+        for (int i = t * V; i < P; i += GS * V) {
+            in_vec<T, V> r, o;
+            if (rs) r = *reinterpret_cast<const in_vec<T, V> *>(rs + i);
+#pragma unroll
+            for (int u = 0; u < V; ++u) {
+                float v = ((buf[i + u] - m0) - dm) * sc + bt;
+                if (rs) v += (float)r.v[u];
+                if (relu) v = fmaxf(v, 0.f);
+                o.v[u] = (T)v;
+            }
+            *reinterpret_cast<in_vec<T, V> *>(dst + i) = o;
+        }
+    } else {
+        for (int i = t; i < P; i += GS) {
+            float v = ((buf[i] - m0) - dm) * sc + bt;
+            if (rs) v += (float)rs[i];
+            if (relu) v = fmaxf(v, 0.f);
+            dst[i] = (T)v;
+        }
+    }
+}
+
+// Planes over IN_RESIDENT_PX: one block per plane, the same arithmetic with the plane read from
+// global memory in each of the three passes.
+template <typename T>
+__global__ __launch_bounds__(IN_T) void k_instnorm_loop(const T *x, const T *res,
+                                                        const float *gamma, const float *beta,
+                                                        int C, int P, int relu, T *y) {
+    __shared__ float red[5][IN_T / WAVE];
+    const int t = threadIdx.x;
+    const long long pl = blockIdx.x;
+    const T *src = x + pl * P;
+    float m0, dm, inv;
+    in_stats<IN_T>(
+        P, t, true, red,
+        [&](float &s, float &lo, float &hi) {
+            for (int i = t; i < P; i += IN_T) {
+                const float f = (float)src[i];
+                s += f;
+                lo = fminf(lo, f);
+                hi = fmaxf(hi, f);
+            }
+        },
+        [&](int i) { return (float)src[i]; }, &m0, &dm, &inv);
+    const int c = (int)(pl % C);
+    const float sc = gamma[c] * inv, bt = beta[c];
+    T *dst = y + pl * P;
+    const T *rs = res ? res + pl * P : nullptr;
+    for (int i = t; i < P; i += IN_T) {
+        float v = (((float)src[i] - m0) - dm) * sc + bt;
+        if (rs) v += (float)rs[i];
+        if (relu) v = fmaxf(v, 0.f);
+        dst[i] = (T)v;
+    }
+}
+
 // --------------------------------------------------------------------------------------- k_gate
 // ChannelGate (osnet.py): pooled = plane sums / P (rounded to T, as the graph's .to(dtype)),
 // hidden = relu(W1 pooled + b1), gate = sigmoid(W2 hidden + b2), for the four branches of a
@@ -378,6 +602,47 @@ __global__ __launch_bounds__(256) void k_gate(const float *psum, float inv_p, co
 }  // namespace yta
 
 using namespace yta;
+
+template <bool RELU>
+static int stem_launch(const void *x, int N, int H, int W, const float *w, const float *b, int C0,
+                       int half, void *y, void *stream) {
+    YTA_CHECK(x && w && b && y && N > 0 && H > 0 && W > 0 && C0 > 0 && C0 % 16 == 0,
+              YTA_ERR_INVALID, "bad stem arguments (C0 a multiple of 16)");
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const dim3 g((Wo + ST_TILE - 1) / ST_TILE, (Ho + ST_TILE - 1) / ST_TILE, N);
+    const size_t lds = sizeof(float) * 147 * C0;
+    if (half)
+        hipLaunchKernelGGL((k_stem<_Float16, 16, RELU>), g, dim3(256), lds, (hipStream_t)stream,
+                           (const _Float16 *)x, H, W, w, b, C0, (_Float16 *)y, Ho, Wo);
+    else
+        hipLaunchKernelGGL((k_stem<float, 16, RELU>), g, dim3(256), lds, (hipStream_t)stream,
+                           (const float *)x, H, W, w, b, C0, (float *)y, Ho, Wo);
+    YTA_HIP(hipGetLastError());
+    return YTA_OK;
+}
+
+// Threads per plane by plane size: 16 lanes up to 128 pixels (the 16 x 8 planes of stage 4 and
+// below), a wave up to 512 (stage 3), the block beyond.
+template <typename T, bool POOL>
+static void instnorm_launch(const void *x, const void *res, const float *gamma, const float *beta,
+                            long long planes, int C, int P, int relu, void *y, int H, int W,
+                            hipStream_t st) {
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const int V = 16 / (int)sizeof(T);
+    const bool al = ((uintptr_t)x | (POOL ? 0 : (uintptr_t)y) | (uintptr_t)res) % 16 == 0;
+    const int vec = al && P % V == 0;
+    const int gs = P <= 128 ? 16 : (P <= 512 ? 64 : IN_T), ppb = IN_T / gs;
+    const dim3 g((unsigned)((planes + ppb - 1) / ppb));
+    const size_t lds = sizeof(float) * ppb * ((P + 3) & ~3);
+#define YTA_IN_LAUNCH(GS)                                                                       \
+    hipLaunchKernelGGL((k_instnorm<T, GS, POOL>), g, dim3(IN_T), lds, st, (const T *)x,         \
+                       (const T *)res, gamma, beta, planes, C, P, vec, relu, (T *)y, H, W, Ho,  \
+                       Wo)
+    if (gs == 16) YTA_IN_LAUNCH(16);
+    else if (gs == 64) YTA_IN_LAUNCH(64);
+    else YTA_IN_LAUNCH(IN_T);
+#undef YTA_IN_LAUNCH
+}
 
 extern "C" {
 
@@ -459,17 +724,55 @@ int yta_osnet_pointwise(const yta_pw_args *args, int half, void *stream) {
 
 int yta_osnet_stem(const void *x, int N, int H, int W, const float *w, const float *b, int C0,
                    int half, void *y, void *stream) {
-    YTA_CHECK(x && w && b && y && N > 0 && H > 0 && W > 0 && C0 > 0 && C0 % 16 == 0,
-              YTA_ERR_INVALID, "bad stem arguments (C0 a multiple of 16)");
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const dim3 g((Wo + ST_TILE - 1) / ST_TILE, (Ho + ST_TILE - 1) / ST_TILE, N);
-    const size_t lds = sizeof(float) * 147 * C0;
-    if (half)
-        hipLaunchKernelGGL((k_stem<_Float16, 16>), g, dim3(256), lds, (hipStream_t)stream,
-                           (const _Float16 *)x, H, W, w, b, C0, (_Float16 *)y, Ho, Wo);
-    else
-        hipLaunchKernelGGL((k_stem<float, 16>), g, dim3(256), lds, (hipStream_t)stream,
-                           (const float *)x, H, W, w, b, C0, (float *)y, Ho, Wo);
+    return stem_launch<true>(x, N, H, W, w, b, C0, half, y, stream);
+}
+
+int yta_osnet_stem_linear(const void *x, int N, int H, int W, const float *w, const float *b,
+                          int C0, int half, void *y, void *stream) {
+    return stem_launch<false>(x, N, H, W, w, b, C0, half, y, stream);
+}
+
+int yta_osnet_instnorm_resident(void) { return IN_RESIDENT_PX; }
+
+int yta_osnet_instnorm(const void *x, const void *res, const float *gamma, const float *beta,
+                       int N, int C, int P, int relu, int half, void *y, void *stream) {
+    YTA_CHECK(x && gamma && beta && y && N > 0 && C > 0 && P > 0, YTA_ERR_INVALID,
+              "bad instance norm arguments");
+    const long long planes = (long long)N * C;
+    YTA_CHECK(planes <= 0x7fffffffLL, YTA_ERR_INVALID, "grid too large");
+    hipStream_t st = (hipStream_t)stream;
+    if (P <= IN_RESIDENT_PX) {
+        if (half) instnorm_launch<_Float16, false>(x, res, gamma, beta, planes, C, P, relu, y, 1, P, st);
+        else instnorm_launch<float, false>(x, res, gamma, beta, planes, C, P, relu, y, 1, P, st);
+    } else if (half) {
+        hipLaunchKernelGGL(k_instnorm_loop<_Float16>, dim3((unsigned)planes), dim3(IN_T), 0, st,
+                           (const _Float16 *)x, (const _Float16 *)res, gamma, beta, C, P, relu,
+                           (_Float16 *)y);
+    } else {
+        hipLaunchKernelGGL(k_instnorm_loop<float>, dim3((unsigned)planes), dim3(IN_T), 0, st,
+                           (const float *)x, (const float *)res, gamma, beta, C, P, relu,
+                           (float *)y);
+    }
+    YTA_HIP(hipGetLastError());
+    return YTA_OK;
+}
+
+int yta_osnet_instnorm_maxpool(const void *x, const float *gamma, const float *beta, int N, int C,
+                               int H, int W, int half, void *work, void *y, void *stream) {
+    YTA_CHECK(x && gamma && beta && y && N > 0 && C > 0 && H > 0 && W > 0 &&
+                  (long long)H * W <= 0x7fffffffLL,
+              YTA_ERR_INVALID, "bad instance norm arguments");
+    const long long planes = (long long)N * C;
+    YTA_CHECK(planes <= 0x7fffffffLL, YTA_ERR_INVALID, "grid too large");
+    const int P = H * W;
+    if (P > IN_RESIDENT_PX) {
+        YTA_CHECK(work, YTA_ERR_INVALID, "plane over the resident bound: work must hold the input");
+        const int rc = yta_osnet_instnorm(x, nullptr, gamma, beta, N, C, P, 1, half, work, stream);
+        return rc != YTA_OK ? rc : yta_osnet_pool(work, N, C, H, W, 0, half, y, stream);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (half) instnorm_launch<_Float16, true>(x, nullptr, gamma, beta, planes, C, P, 1, y, H, W, st);
+    else instnorm_launch<float, true>(x, nullptr, gamma, beta, planes, C, P, 1, y, H, W, st);
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
