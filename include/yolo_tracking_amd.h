@@ -1036,7 +1036,7 @@ int yta_osnet_gate_sum(const void *stack, const void *gate, int N, int C, int P,
  *                                 + sum_{k < k2} w[g][k1 + k][co] x2[n][k][p]
  *                                 + bias[g cout_g + co] + res[n][g cout_g + co][p] )
  * w: float32 [G][k1 + k2][cout_g] (k-major: BatchNorm folded, transposed); bias, x2 (k2 = 0),
- * res may be NULL. */
+ * res may be NULL.  relu: 0 none, 1 ReLU, 2 ReLU6 (clamp to [0, 6]: mobilenetv2.py ConvBlock). */
 typedef struct yta_pw_args {
     const void *x1;
     long long x1n, x1c, x1p;
@@ -1085,6 +1085,34 @@ int yta_osnet_instnorm_maxpool(const void *x, const float *gamma, const float *b
                                int H, int W, int half, void *work, void *y, void *stream);
 int yta_osnet_stem_linear(const void *x, int N, int H, int W, const float *w, const float *b,
                           int C0, int half, void *y, void *stream);
+
+/* ---- MobileNetV2 (boxmot/appearance/backbones/mobilenetv2.py; appearance/mobilenetv2.py).  The
+ * same conventions as the OSNet kernels: device pointers, asynchronous on `stream`, NCHW planes,
+ * float32 (half = 0) or float16 (half = 1) storage, float32 arithmetic, BatchNorms folded into
+ * float32 weights and biases, no floating-point atomics (the same input gives the same bits).
+ * The projection (Bottleneck.conv3, :52-55 and :60, + the residual of :61-62), conv9 (:102,
+ * :177) and an unfused expand are yta_osnet_pointwise (relu = 0 / 2 / 2); the global mean (:182)
+ * is yta_osnet_pool kind 2.
+ * yta_mbv2_stem: conv1 = ConvBlock(3, C0, 3, s=2, p=1) (:94, :39-40): w float32 C0 x 3 x 3 x 3,
+ * C0 in 1..64, + b, clamp to [0, 6]: x N x 3 x H x W -> y N x C0 x ((H-1)/2+1) x ((W-1)/2+1).
+ * yta_mbv2_dw3x3: Bottleneck.dwconv2 = ConvBlock(C, C, 3, stride, 1, g=C) (:49-51): depthwise 3x3,
+ * zero padding 1, stride 1 or 2 (w C x 9) + b[c], clamp to [0, 6]: x N x C x H x W ->
+ * y N x C x ((H-1)/stride+1) x ((W-1)/stride+1).
+ * yta_mbv2_expand_dw: Bottleneck.conv1 and .dwconv2 (:58-59) in one launch,
+ *   y = relu6(dw3x3_stride(relu6(W1 x + b1)) + b2),  x N x Cin x H x W -> y N x Cmid x Ho x Wo,
+ * w1 float32 [Cin][Cmid] (k-major, as yta_osnet_pointwise takes it), wdw Cmid x 9.  The Cmid-channel
+ * expanded activation exists only in LDS and registers, and the depthwise filter zero-pads THAT
+ * activation: a tap outside the image contributes 0, not relu6(b1).  The value between the two
+ * layers stays float32 even with float16 storage, so with half = 1 this is one rounding closer to
+ * the reference's float32 result than yta_osnet_pointwise followed by yta_mbv2_dw3x3, which stores
+ * the expanded tensor as float16 in between.  Cin, Cmid, H and W are arbitrary. */
+int yta_mbv2_stem(const void *x, int N, int H, int W, const float *w, const float *b, int C0,
+                  int half, void *y, void *stream);
+int yta_mbv2_dw3x3(const void *x, const float *w, const float *b, int N, int C, int H, int W,
+                   int stride, int half, void *y, void *stream);
+int yta_mbv2_expand_dw(const void *x, const float *w1, const float *b1, const float *wdw,
+                       const float *b2, int N, int Cin, int Cmid, int H, int W, int stride,
+                       int half, void *y, void *stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,11 @@ detections (1920x1080 BGR, one yta_reid_preprocess_device launch) + the OSNet fo
 (appearance/osnet.py: folded BatchNorms, channels-last, batched branches; random weights of the
 named variant, any key of appearance/osnet.py VARIANTS: the plain widths, osnet_ibn_* and
 osnet_ain_* with their instance norms) + global normalisation, features left on the device.  Reports crops/s for the
-network alone and for the whole get_features path, float32 and float16.  Prints JSON lines."""
+network alone and for the whole get_features path, float32 and float16.  Prints JSON lines.
+--variant mobilenetv2_x1_0 / mobilenetv2_x1_4 (appearance/mobilenetv2.py) runs the same measurement
+on MobileNetV2: the HIP forward with the fused expand + depthwise kernel ("fused": true), with the
+two layers as two launches ("fused": false), and the same folded graph on PyTorch's kernels in
+NHWC and NCHW ("hip_blocks": false), the baseline a model=<torch module> user gets."""
 import argparse
 import json
 import os
@@ -18,14 +22,17 @@ sys.path.insert(0, REPO)
 
 def main():
     ap = argparse.ArgumentParser()
+    from yolo_tracking_amd.appearance.mobilenetv2 import VARIANTS as MBV2
     from yolo_tracking_amd.appearance.osnet import VARIANTS
-    ap.add_argument("--variant", default="osnet_x0_25", choices=sorted(VARIANTS),
-                    help="OSNet variant: plain, osnet_ibn_* or osnet_ain_* (default osnet_x0_25)")
+    ap.add_argument("--variant", default="osnet_x0_25", choices=sorted(VARIANTS) + sorted(MBV2),
+                    help="OSNet variant (plain, osnet_ibn_* or osnet_ain_*; default osnet_x0_25) "
+                         "or mobilenetv2_x1_0 / mobilenetv2_x1_4")
     ap.add_argument("--crops", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=10)
     args = ap.parse_args()
     import torch
     from yolo_tracking_amd.appearance import ReIDDetectMultiBackend
+    from yolo_tracking_amd.appearance.mobilenetv2 import MobileNetV2ReID
     from yolo_tracking_amd.appearance.osnet import OSNetReID
     rng = np.random.default_rng(0)
     H, W, n = 1080, 1920, args.crops
@@ -33,12 +40,23 @@ def main():
     wh = rng.uniform(48, 192, (n, 2))
     xy = rng.uniform(0, 1, (n, 2)) * [W - 200, H - 200]
     boxes = np.concatenate([xy, xy + wh], 1)
-    for half, chunk, hip, cl in ((False, 1024, True, False), (True, 1024, True, False),
-                                 (False, 256, True, False), (True, 256, True, False),
-                                 (False, 1024, False, True), (True, 1024, False, True),
-                                 (True, 1024, False, False)):
-        net = OSNetReID(args.variant, None, device="cuda:0", half=half, chunk=chunk,
-                        channels_last=cl, hip=hip)
+    mbv2 = args.variant in MBV2
+    if mbv2:   # (half, chunk, hip, channels_last, fused)
+        configs = [(half, 1024, hip, cl, fused) for half in (False, True)
+                   for hip, cl, fused in ((True, False, True), (True, False, False),
+                                          (False, True, None), (False, False, None))]
+    else:
+        configs = [c + (None,) for c in (
+            (False, 1024, True, False), (True, 1024, True, False), (False, 256, True, False),
+            (True, 256, True, False), (False, 1024, False, True), (True, 1024, False, True),
+            (True, 1024, False, False))]
+    for half, chunk, hip, cl, fused in configs:
+        if mbv2:
+            net = MobileNetV2ReID(args.variant, None, device="cuda:0", half=half, chunk=chunk,
+                                  channels_last=cl, hip=hip, fused=bool(fused))
+        else:
+            net = OSNetReID(args.variant, None, device="cuda:0", half=half, chunk=chunk,
+                            channels_last=cl, hip=hip)
         reid = ReIDDetectMultiBackend(None, device=0, fp16=half, model=net)
         crops = reid.preprocess(boxes, img)
         if half:
@@ -59,7 +77,8 @@ def main():
         for _ in range(args.steps):
             reid.get_features(boxes, img)
         e2e_ms = 1000 * (time.perf_counter() - t0) / args.steps
-        print(json.dumps({"metric": "OSNet ReID crops/s", "variant": args.variant,
+        print(json.dumps({"metric": ("MobileNetV2" if mbv2 else "OSNet") + " ReID crops/s",
+                          "variant": args.variant, "fused": fused,
                           "dtype": "f16" if half else "f32", "crops": n, "chunk": chunk,
                           "layout": "nhwc" if cl else "nchw", "hip_blocks": hip,
                           "network_ms": net_ms, "network_crops_per_s": n / (net_ms * 1e-3),

@@ -286,6 +286,9 @@ _SIGS = {
     "yta_osnet_instnorm": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P], _I),
     "yta_osnet_instnorm_maxpool": ([_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P], _I),
     "yta_osnet_stem_linear": ([_P, _I, _I, _I, _P, _P, _I, _I, _P, _P], _I),
+    "yta_mbv2_stem": ([_P, _I, _I, _I, _P, _P, _I, _I, _P, _P], _I),
+    "yta_mbv2_dw3x3": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
+    "yta_mbv2_expand_dw": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P], _I),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

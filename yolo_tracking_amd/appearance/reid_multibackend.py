@@ -15,7 +15,8 @@ The network: OSNet (appearance/osnet.py, an eval-mode inference graph with folde
 channels-last, batched branches) built from `weights` as the reference builds it from the weight
 file name (reid_multibackend.py:57-80): osnet_x0_25 .. osnet_x1_0, and the instance-norm members
 of the family, osnet_ibn_x1_0 and osnet_ain_x1_0 (and their narrower widths), whose norms run in
-csrc/osnet.hip as well; the reference's .pt state dicts
+csrc/osnet.hip as well, or MobileNetV2 (appearance/mobilenetv2.py: mobilenetv2_x1_0 and
+mobilenetv2_x1_4, csrc/mbv2.hip); the reference's .pt state dicts
 load unchanged (torch.load(weights_only=True)).  A weight file that is not on disk would be
 downloaded by the reference (gdown, :61-64) or end the program (:67-72); there is no network here,
 so a missing file raises FileNotFoundError.  Freshly initialised weights (benchmarks, plumbing
@@ -103,18 +104,23 @@ class ReIDDetectMultiBackend:
         self.model = model
 
     def _build_osnet(self, weights):
-        """reid_multibackend.py:57-80 for the OSNet family: the plain widths (the trackers'
-        default weights), osnet_ibn_* and osnet_ain_* (appearance/osnet.py VARIANTS)."""
-        from .osnet import OSNetReID, load_checkpoint, model_name
-        name = model_name(weights)
-        if name is None:
+        """reid_multibackend.py:57-80 as a dispatch on the weight file name: the OSNet family
+        first (the plain widths, the trackers' default weights, osnet_ibn_* and osnet_ain_*:
+        appearance/osnet.py VARIANTS), then MobileNetV2 (appearance/mobilenetv2.py VARIANTS)."""
+        from . import mobilenetv2, osnet
+        for family, cls in ((osnet, osnet.OSNetReID), (mobilenetv2, mobilenetv2.MobileNetV2ReID)):
+            name = family.model_name(weights)
+            if name is not None:
+                break
+        else:
             raise NotImplementedError(
                 f"ReID weights {str(weights)!r}: only the OSNet family (osnet_x0_25 .. osnet_x1_0, "
-                "osnet_ibn_x1_0, osnet_ain_x1_0 and their other widths) is rebuilt on the MI355X "
-                "path; pass model=<torch module> for other networks")
+                "osnet_ibn_x1_0, osnet_ain_x1_0 and their other widths) and MobileNetV2 "
+                "(mobilenetv2_x1_0, mobilenetv2_x1_4) are rebuilt on the MI355X path; pass "
+                "model=<torch module> for other networks")
         w = Path(weights)
         if w.is_file():
-            sd = load_checkpoint(w)
+            sd = osnet.load_checkpoint(w)
         elif self.random_init:
             warnings.warn(f"ReID weights {str(w)!r} not on disk: {name} runs with fresh random "
                           "weights (random_init=True)", RuntimeWarning, stacklevel=3)
@@ -124,7 +130,7 @@ class ReIDDetectMultiBackend:
                 f"ReID weights {str(w)!r} not found and there is no network to download them "
                 f"(reid_multibackend.py:61-72); pass an existing {name} checkpoint, model=<torch "
                 "module>, or random_init=True for untrained weights")
-        return OSNetReID(name, sd, device=self.device, half=self.fp16)
+        return cls(name, sd, device=self.device, half=self.fp16)
 
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
