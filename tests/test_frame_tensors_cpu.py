@@ -49,3 +49,7 @@ def test_shared_header_is_a_build_dependency():
     for src in ("cmc.hip", "ecc.hip"):
         with open(os.path.join(csrc, src)) as f:
             assert '#include "cmc_tensors.hpp"' in f.read(), src
+    # the protocol itself (slots, hand-off) is tensor_path.hpp's
+    assert "tensor_path.hpp" in hdrs and os.path.isfile(os.path.join(csrc, "tensor_path.hpp"))
+    with open(os.path.join(csrc, "cmc_tensors.hpp")) as f:
+        assert '#include "tensor_path.hpp"' in f.read()

@@ -243,6 +243,43 @@ def test_feature_width_8_takes_the_guarded_loads():
     assert len(eng.state(0)["id"]) == 3
 
 
+def test_many_streams():
+    """S = 1030: the output-offset scan (one 1024-thread block) gives some threads two streams and
+    the last ones none.  Every stream sees 0..3 of its three objects a frame; update_tensors on one
+    engine against update() on a second, bit for bit."""
+    S, F = 1030, 4
+    rng = np.random.default_rng(1030)
+    base = rng.standard_normal((3, 8)).astype(np.float32)
+    box = np.array([[10, 10, 50, 90], [200, 40, 260, 160], [400, 300, 470, 420]], dtype=np.float64)
+    kw = dict(feat_dim=8, track_capacity=8, max_dets=4)
+    ten, host = _engine(S, SMALL_P, **kw), _engine(S, SMALL_P, **kw)
+    seen, n_rows = np.zeros(S, bool), 0
+    for f in range(F):
+        counts = rng.integers(0, 4, size=S)
+        counts[[0, 1023, 1024, 1029]] = np.maximum(counts[[0, 1023, 1024, 1029]], 1)
+        counts[5 + f] = 0   # at least one stream without a detection in every frame
+        dets, feats = [], []
+        for s in range(S):
+            pick = np.sort(rng.permutation(3)[:counts[s]])
+            b = box[pick] + 2.0 * f + 0.25 * (s % 7)
+            dets.append(np.concatenate([b, np.full((len(pick), 1), 0.8), np.zeros((len(pick), 1))],
+                                       axis=1))
+            feats.append(base[pick] + np.float32(0.01) *
+                         rng.standard_normal((len(pick), 8)).astype(np.float32))
+        seen |= counts > 0
+        exp = host.update(dets, feats)
+        out = ten.update_tensors(_t(np.concatenate(dets)), _t(np.concatenate(feats)),
+                                 counts=counts.tolist())
+        _check_frame(out, exp, f"frame {f}")   # rows, offsets, row_stream (-1 from offsets[S] on)
+        assert int(out[1][S]) == sum(len(e) for e in exp)
+        n_rows += int(out[1][S])
+        assert np.array_equal(ten.n_tracks(), host.n_tracks()), f
+    assert n_rows > 0   # the first frame's births report no row; the later frames do
+    assert seen[[0, 1023, 1024, 1029]].all() and (counts == 0).any()
+    ten.sync()   # no stream outgrew track_capacity
+    assert host.n_tracks().max() <= 8
+
+
 # ------------------------------------------------------------------------------------- 3. warps
 def test_device_warps_with_nan_rows(ref):
     p, seq, rows, gates, states, _ = ref("f64")

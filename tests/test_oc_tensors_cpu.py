@@ -63,4 +63,8 @@ def test_engines_have_the_methods():
 
 def test_makefile_lists_the_kernels_header():
     mk = open(os.path.join(REPO, "yolo_tracking_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^HDRS\s*=.*\boc_tensors\.hpp\b", mk, re.M)
+    # the family's tensor kernels are tensor_path.hpp's, which oc_host.hpp includes
+    assert re.search(r"^HDRS\s*=.*\btensor_path\.hpp\b", mk, re.M)
+    assert re.search(r"^HDRS\s*=.*\boc_host\.hpp\b", mk, re.M)
+    host = open(os.path.join(REPO, "yolo_tracking_amd", "csrc", "oc_host.hpp")).read()
+    assert '#include "tensor_path.hpp"' in host

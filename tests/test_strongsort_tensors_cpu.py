@@ -64,7 +64,8 @@ def test_engine_surface():
 
 def test_makefile_lists_the_new_header():
     csrc = os.path.join(REPO, "yolo_tracking_amd", "csrc")
-    assert os.path.isfile(os.path.join(csrc, "ss_tensors.hpp"))
+    # the tensor path's kernels and slots: tensor_path.hpp, shared by every engine
+    assert os.path.isfile(os.path.join(csrc, "tensor_path.hpp"))
     mk = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
-    assert "ss_tensors.hpp" in re.search(r"^HDRS\s*=(.*)$", mk, re.M).group(1).split()
-    assert '#include "ss_tensors.hpp"' in open(os.path.join(csrc, "strongsort.hip")).read()
+    assert "tensor_path.hpp" in re.search(r"^HDRS\s*=(.*)$", mk, re.M).group(1).split()
+    assert '#include "tensor_path.hpp"' in open(os.path.join(csrc, "strongsort.hip")).read()

@@ -33,6 +33,7 @@
 #include "bytetrack.hpp"
 #include "host_pool.hpp"
 #include "oc_host.hpp"   // dalloc / DALLOC, grow_pair
+#include "tensor_path.hpp"
 
 namespace yta {
 namespace {
@@ -2596,106 +2597,14 @@ __global__ __launch_bounds__(256) void k_widen_f32(const float *src, double *dst
     }
 }
 
-// Tensor path (yta_bytetrack_update_tensors), one launch for everything a frame brings in.
-// Block 0: the S + 1 detection offsets as the prefix sums of the frame's per-stream counts, which
-// it reads straight from the call's page-locked staging (mapped host memory, 4 B a stream), and,
-// when the caller passed ID counters, cnt[s].next_id from the same staging.  Blocks 1..: the
-// caller's detection rows (`stride` elements apart, of type T) widened exactly into the packed
-// float64 rows the kernels read; a thread takes two neighbouring columns of one row (6 is even, so
-// a pair never straddles rows) with two scalar loads, which any stride and any element alignment
-// allow, and one 16-B store.  Bytes per detection: 6 * sizeof(T) read (plus the stride's padding
-// where lines are shared), 48 written: at most 96.
-constexpr int ING_T = 256;
-template <typename T>
-__global__ __launch_bounds__(ING_T) void k_ingest(const T *src, long long stride, long long rows,
-                                                  double *dst, const int *counts,
-                                                  const long long *nid, int S, int *off,
-                                                  BtCounters *cnt) {
-    const int t = threadIdx.x;
-    if (blockIdx.x == 0) {
-        __shared__ int part[ING_T];
-        const int per = (S + ING_T - 1) / ING_T, s0 = min(S, t * per), s1 = min(S, s0 + per);
-        int sum = 0;
-        for (int s = s0; s < s1; ++s) sum += max(counts[s], 0);
-        part[t] = sum;
-        __syncthreads();
-        for (int d = 1; d < ING_T; d <<= 1) {   // inclusive Hillis-Steele scan
-            const int v = t >= d ? part[t - d] : 0;
-            __syncthreads();
-            part[t] += v;
-            __syncthreads();
-        }
-        int r = part[t] - sum;   // exclusive prefix of this thread's run
-        if (t == 0) off[0] = 0;
-        for (int s = s0; s < s1; ++s) {
-            r += max(counts[s], 0);
-            off[s + 1] = r;
-            if (nid) cnt[s].next_id = nid[s];
-        }
-        return;
-    }
-    const long long pairs = rows * 3, step = (long long)(gridDim.x - 1) * ING_T;
-    for (long long k = (long long)(blockIdx.x - 1) * ING_T + t; k < pairs; k += step) {
-        const long long row = k / 3;
-        const T *p = src + row * stride + 2 * (k - row * 3);
-        reinterpret_cast<double2 *>(dst)[k] = make_double2((double)p[0], (double)p[1]);
-    }
-}
-
-// Tensor path: every stream's output rows (src + s * cap_rows * 8) moved to the caller's packed
-// rows at the prefix offsets, with the stream id of each row beside them (row_stream, -1 from
-// off[S] to `limit`, the caller's capacity, which no row or id is written past), and the
-// stream's live-track counts after the frame stored into the call's page-locked staging (mapped
-// host memory), where the next calls bound the track capacity without a round trip.  Block per
-// stream, 16-B pieces: 64 B read and 64 B written a row, 4 B a row of row_stream.
-__global__ __launch_bounds__(256) void k_pack_rows(const double *src, long long cap_rows,
-                                                    const BtCounters *cnt, int S, const int *off,
-                                                    double *dst, long long limit, int *row_stream,
-                                                    int2 *live) {
-    const int s = blockIdx.x, t = threadIdx.x;
-    const long long b = off[s];
-    const long long n = max(min((long long)off[s + 1], limit) - b, 0LL);
-    const double2 *a = reinterpret_cast<const double2 *>(src + s * cap_rows * 8);
-    double2 *d = reinterpret_cast<double2 *>(dst + b * 8);
-    for (long long k = t; k < n * 4; k += blockDim.x) d[k] = a[k];
-    if (row_stream) {
-        for (long long r = t; r < n; r += blockDim.x) row_stream[b + r] = s;
-        for (long long r = (long long)off[S] + (long long)s * blockDim.x + t; r < limit;
-             r += (long long)S * blockDim.x)
-            row_stream[r] = -1;
-    }
-    if (t == 0 && live) live[s] = make_int2(cnt[s].n_tracked, cnt[s].n_lost);
-}
-
-// Pipelined host-buffer update (any S): the same prefix offsets from one 1024-thread block, each
-// thread summing a run of streams, then a block scan.
-constexpr int OFFS_T = 1024;
-__global__ __launch_bounds__(OFFS_T) void k_out_offsets_scan(const BtCounters *cnt, int S, int cap,
-                                                              int *off, int *off_host) {
-    __shared__ int part[OFFS_T];
-    const int t = threadIdx.x;
-    const int per = (S + OFFS_T - 1) / OFFS_T, s0 = min(S, t * per), s1 = min(S, s0 + per);
-    int sum = 0;
-    for (int s = s0; s < s1; ++s) sum += min(max(cnt[s].n_out, 0), cap);
-    part[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < OFFS_T; d <<= 1) {   // inclusive Hillis-Steele scan
-        const int v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int r = part[t] - sum;   // exclusive prefix of this thread's run
-    if (t == 0) {
-        off[0] = 0;
-        if (off_host) off_host[0] = 0;
-    }
-    for (int s = s0; s < s1; ++s) {
-        r += min(max(cnt[s].n_out, 0), cap);
-        off[s + 1] = r;
-        if (off_host) off_host[s + 1] = r;   // mapped host memory: no copy on the copy-out stream
-    }
-}
+// The tensor path's kernels (k_tp_ingest, k_tp_out_offsets, k_tp_pack_rows) are tensor_path.hpp's;
+// the pipelined host-buffer update launches k_tp_out_offsets too, with its host mirror.
+// k_tp_pack_rows' accessor: a stream's (tracked, lost) counts after the frame into the slot.
+struct BtLive {
+    const BtCounters *cnt;
+    int2 *live;
+    __device__ void operator()(int s) const { live[s] = make_int2(cnt[s].n_tracked, cnt[s].n_lost); }
+};
 
 // Pipelined path: a frame's packed rows (off[S] of them, 64 B each) stored by the copy-out
 // stream's kernel straight into mapped page-locked host memory (the caller's buffer or the slot's
@@ -2972,26 +2881,14 @@ struct yta_bytetrack {
     size_t ev_used = 0;
     // host-buffer staging copies: persistent worker threads (created on the first large copy)
     std::unique_ptr<CopyPool> pool;
-    // tensor path (yta_bytetrack_update_tensors): device rows in and out, nothing waited for.
-    // What a call copies from host memory goes through a ring of page-locked, mapped slots, one
-    // per frame in flight, each guarded by the event recorded after its frame's last launch; the
-    // frame's kernels store the streams' live-track counts back into the slot.
-    struct TSlot {
-        hipEvent_t in = nullptr, done = nullptr;   // caller stream -> engine stream -> caller stream
-        int *h_counts = nullptr, *m_counts = nullptr;        // S detection counts (host / device view)
-        long long *h_nid = nullptr, *m_nid = nullptr;        // S ID counters
-        int2 *h_live = nullptr, *m_live = nullptr;           // S x (tracked, lost) after the frame
-        std::vector<long long> cum_at;   // t_cum after this frame was enqueued
-        long long seq = -1, gen = -1;    // enqueue order; the t_gen it belongs to
-    };
-    std::vector<TSlot *> t_ring;
-    std::vector<long long> t_cum;        // per stream: detections enqueued by tensor frames so far
-    std::vector<long long> t_base_live, t_base_cum;   // h_cnt's live tracks and t_cum when it was exact
-    bool t_dirty = false;                // tensor frames enqueued since h_cnt was last read
-    long long t_seq = 0, t_gen = 0;      // t_gen: bumped whenever h_cnt is made exact again
-    double *t_det = nullptr;             // float64 staging rows (k_ingest)
+    // tensor path (yta_bytetrack_update_tensors, protocol: tensor_path.hpp): device rows in and
+    // out, nothing waited for.  A slot (bt_slot_view) carries the call's counts and ID counters
+    // in and the streams' live-track counts back.
+    FrameRing t_ring;
+    TrackBound t_bound;                  // live tracks: h_cnt's n_tracked + n_lost
+    double *t_det = nullptr;             // float64 staging rows (k_tp_ingest)
     long long t_det_cap = 0;
-    int *t_off = nullptr;                // S + 1 detection offsets (k_ingest)
+    int *t_off = nullptr;                // S + 1 detection offsets (k_tp_ingest)
     float *t_feat = nullptr;             // BoT-SORT: feature rows gathered from a strided tensor
     long long t_feat_cap = 0;
     std::vector<void *> t_retired;       // outgrown staging a queued frame may still read: freed
@@ -3547,17 +3444,15 @@ int read_counters(yta_bytetrack *e) {
     YTA_HIP(host_wait(e->stream));
     // every tensor frame enqueued so far has run: h_cnt is exact again, and nothing reads the
     // staging those frames outgrew
-    e->t_dirty = false;
-    ++e->t_gen;
-    for (void *p : e->t_retired) (void)hipFree(p);
-    e->t_retired.clear();
+    e->t_bound.exact();
+    tensor_free_retired(e->t_retired);
     return YTA_OK;
 }
 
 // After tensor frames (yta_bytetrack_update_tensors), which read nothing back: wait for them and
 // bring h_cnt up to date, for the entry points that size or report from it.
 int tensor_catch_up(yta_bytetrack *e) {
-    if (!e->t_dirty) return YTA_OK;
+    if (!e->t_bound.dirty) return YTA_OK;
     YTA_HIP(hipSetDevice(e->device));
     return read_counters(e);
 }
@@ -4007,7 +3902,7 @@ int pipe_slot_ready(yta_bytetrack *e, yta_bytetrack::PipeSlot &p, long long dets
         YTA_HIP(hipHostGetDevicePointer((void **)&p.m_off, p.h_off, 0));
         YTA_HIP(hipMalloc((void **)&p.d_pack_off, sizeof(int) * (S + 1)));
         // counters and row offsets: written by the compute stream's kernels straight into mapped,
-        // coherent host memory (k_out_offsets_scan, k_cnt_to_host)
+        // coherent host memory (k_tp_out_offsets, k_cnt_to_host)
         const unsigned mf = hipHostMallocMapped | hipHostMallocCoherent;
         YTA_HIP(hipHostMalloc((void **)&p.h_pack_off, sizeof(int) * (S + 1), mf));
         YTA_HIP(hipHostMalloc((void **)&p.h_cnt, sizeof(BtCounters) * S, mf));
@@ -4093,8 +3988,9 @@ int pipe_enqueue_run(yta_bytetrack *e, yta_bytetrack::PipeSlot &p, const long lo
     rc = launch_pipeline(e, p.d_in, p.d_off, e->out_own, nullptr);
     if (rc) return rc;
     e->pstat[PS_LAUNCH_MS] += ms_since(tl);
-    hipLaunchKernelGGL(k_out_offsets_scan, dim3(1), dim3(OFFS_T), 0, e->stream, e->a.cnt, S,
-                       e->CAP, p.d_pack_off, p.m_pack_off);
+    hipLaunchKernelGGL(k_tp_out_offsets<CountersNOut<BtCounters>>, dim3(1), dim3(TP_OFFS_T), 0,
+                       e->stream, CountersNOut<BtCounters>{e->a.cnt}, S, e->CAP, p.d_pack_off,
+                       p.m_pack_off);
     hipLaunchKernelGGL(k_pack_out, dim3(S), dim3(256), 0, e->stream, e->out_own, (long long)e->CAP,
                        p.d_pack_off, p.d_pack, p.pack_cap);
     hipLaunchKernelGGL(k_cnt_to_host, dim3((S * 8 + 255) / 256), dim3(256), 0, e->stream,
@@ -4279,92 +4175,36 @@ int pipe_collect(yta_bytetrack *e, long long *next_id, int *out_offsets) {
 }
 
 // ---- tensor path: device rows in, device rows out, stream-ordered ------------------------------
-// The caller's stream hands over to the engine's stream through an event, the frame runs there as
-// plain launches (k_ingest, the frame's kernels, k_out_offsets_scan, k_pack_rows), and a second
-// event hands back: nothing is waited for on the host unless the capacity bound below fails.
+// The protocol is tensor_path.hpp's: the frame runs on the engine's stream as plain launches
+// (k_tp_ingest, the frame's kernels, k_tp_out_offsets, k_tp_pack_rows), and nothing is waited for
+// on the host unless the capacity bound below fails.
 enum { TS_FRAMES, TS_HOST_WAITS, TS_RESERVES, TS_INGEST_SKIPPED, TS_N };
-constexpr size_t T_RING_MAX = 64;   // frames in flight before a call waits for the oldest
 
-void tensor_free(yta_bytetrack *e) {
-    for (auto *p : e->t_ring) {
-        if (p->in) (void)hipEventDestroy(p->in);
-        if (p->done) (void)hipEventDestroy(p->done);
-        for (void *h : {(void *)p->h_counts, (void *)p->h_nid, (void *)p->h_live})
-            if (h) (void)hipHostFree(h);
-        delete p;
-    }
-    e->t_ring.clear();
-    for (void *d : {(void *)e->t_det, (void *)e->t_off, (void *)e->t_feat})
-        if (d) (void)hipFree(d);
-    for (void *d : e->t_retired) (void)hipFree(d);
-    e->t_retired.clear();
-    e->t_det = nullptr;
-    e->t_off = nullptr;
-    e->t_feat = nullptr;
-}
-
-int tensor_slot_new(yta_bytetrack *e, yta_bytetrack::TSlot **out) {
-    auto *p = new (std::nothrow) yta_bytetrack::TSlot();
-    YTA_CHECK(p, YTA_ERR_NOMEM, "out of host memory");
-    e->t_ring.push_back(p);   // owned from here on (tensor_free)
-    const size_t S = e->S;
-    const unsigned mf = hipHostMallocMapped | hipHostMallocCoherent;
-    YTA_HIP(hipEventCreateWithFlags(&p->in, hipEventDisableTiming));
-    YTA_HIP(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
-    YTA_HIP(hipHostMalloc((void **)&p->h_counts, sizeof(int) * S, mf));
-    YTA_HIP(hipHostMalloc((void **)&p->h_nid, sizeof(long long) * S, mf));
-    YTA_HIP(hipHostMalloc((void **)&p->h_live, sizeof(int2) * S, mf));
-    YTA_HIP(hipHostGetDevicePointer((void **)&p->m_counts, p->h_counts, 0));
-    YTA_HIP(hipHostGetDevicePointer((void **)&p->m_nid, p->h_nid, 0));
-    YTA_HIP(hipHostGetDevicePointer((void **)&p->m_live, p->h_live, 0));
-    p->cum_at.assign(S, 0);
-    *out = p;
-    return YTA_OK;
-}
-
-bool tensor_slot_done(yta_bytetrack::TSlot *p) {
-    if (p->seq < 0) return true;   // never used
-    if (hipEventQuery(p->done) == hipSuccess) return true;
-    (void)hipGetLastError();   // hipErrorNotReady
-    return false;
-}
-
-// A slot no queued frame reads: one whose frame has run, else a new one; with T_RING_MAX frames
-// in flight the call waits for the oldest.
-int tensor_slot_acquire(yta_bytetrack *e, yta_bytetrack::TSlot **out) {
-    yta_bytetrack::TSlot *oldest = nullptr;
-    for (auto *p : e->t_ring) {
-        if (!p->h_live) continue;   // its allocation failed part way
-        if (tensor_slot_done(p)) {
-            *out = p;
-            return YTA_OK;
-        }
-        if (!oldest || p->seq < oldest->seq) oldest = p;
-    }
-    if (e->t_ring.size() < T_RING_MAX || !oldest) return tensor_slot_new(e, out);
-    ++e->tstat[TS_HOST_WAITS];
-    YTA_HIP(hipEventSynchronize(oldest->done));
-    *out = oldest;
-    return YTA_OK;
+// A slot's block: S ID counters and S x (tracked, lost) after the frame (k_tp_pack_rows), then S
+// detection counts.
+struct BtSlotView {
+    long long *nid;
+    int2 *live;
+    int *counts;
+};
+size_t bt_slot_bytes(size_t S) { return S * (8 + 8 + 4); }
+BtSlotView bt_slot_view(void *base, size_t S) {
+    char *b = static_cast<char *>(base);
+    return {reinterpret_cast<long long *>(b), reinterpret_cast<int2 *>(b + 8 * S),
+            reinterpret_cast<int *>(b + 16 * S)};
 }
 
 // Capacity before anything is enqueued.  max_dets from the frame's counts.  Track capacity as
-// pipe_capacity bounds it: a stream's tracked + lost lists after this frame are at most its live
-// tracks after some earlier frame plus every detection enqueued for it since, this frame's
-// included.  The earlier frame is the newest tensor frame whose event has completed (k_pack_rows
-// stored its counts into the slot), else the last exact h_cnt.  Only a bound that does not fit
-// waits for the engine stream and reads the exact counters; only an exact need that does not fit
-// grows the engine, by update_host's geometric rule.
+// pipe_capacity bounds it, through TrackBound.  Only a bound that does not fit waits for the
+// engine stream and reads the exact counters; only an exact need that does not fit grows the
+// engine, by update_host's geometric rule.
 int tensor_capacity(yta_bytetrack *e, const int *counts) {
     const int S = e->S;
-    auto rebase = [&] {   // h_cnt is exact: later frames are bounded from it
-        e->t_base_live.resize(S);
-        for (int s = 0; s < S; ++s)
-            e->t_base_live[s] = (long long)e->h_cnt[s].n_tracked + e->h_cnt[s].n_lost;
-        e->t_base_cum = e->t_cum;
+    TrackBound &bd = e->t_bound;
+    auto rebase = [&] {
+        bd.rebase(S, [&](int s) { return (long long)e->h_cnt[s].n_tracked + e->h_cnt[s].n_lost; });
     };
-    if (e->t_cum.empty()) e->t_cum.assign(S, 0);
-    if (!e->t_dirty) rebase();
+    if (!bd.dirty) rebase();
     int need_d = e->MAXD;
     for (int s = 0; s < S; ++s) need_d = std::max(need_d, counts[s]);
     if (need_d > e->MAXD) {   // reserve() waits for the stream: read the exact counters with it
@@ -4376,24 +4216,18 @@ int tensor_capacity(yta_bytetrack *e, const int *counts) {
         rc = grow_for(e, e->CAP, need_d);
         if (rc) return rc;
     }
-    const yta_bytetrack::TSlot *k0 = nullptr;
-    for (auto *p : e->t_ring)
-        if (p->seq >= 0 && p->gen == e->t_gen && (!k0 || p->seq > k0->seq) && tensor_slot_done(p))
-            k0 = p;
-    bool fits = true;
-    for (int s = 0; s < S && fits; ++s) {
-        const long long live = k0 ? (long long)k0->h_live[s].x + k0->h_live[s].y : e->t_base_live[s];
-        const long long since = e->t_cum[s] - (k0 ? k0->cum_at[s] : e->t_base_cum[s]);
-        fits = live + since + counts[s] <= e->CAP;
-    }
-    if (fits) return YTA_OK;
+    if (bd.fits(e->t_ring, counts, e->CAP, [S](void *h, int s) {
+            const int2 v = bt_slot_view(h, S).live[s];
+            return (long long)v.x + v.y;
+        }))
+        return YTA_OK;
     ++e->tstat[TS_HOST_WAITS];
     int rc = read_counters(e);
     if (rc) return rc;
     rebase();
     int need_c = e->CAP;
     for (int s = 0; s < S; ++s)
-        need_c = std::max<long long>(need_c, e->t_base_live[s] + counts[s]);
+        need_c = std::max<long long>(need_c, bd.base_live[s] + counts[s]);
     if (need_c > e->CAP) {
         ++e->tstat[TS_RESERVES];
         rc = grow_for(e, need_c, e->MAXD);
@@ -4401,98 +4235,53 @@ int tensor_capacity(yta_bytetrack *e, const int *counts) {
     return rc;
 }
 
-// Device staging of at least n elements; an outgrown buffer is kept until the next host wait (a
-// queued frame may still read it).
-template <typename T>
-int tensor_stage(yta_bytetrack *e, T **buf, long long *cap, long long n, long long floor_n) {
-    if (n <= *cap && *buf) return YTA_OK;
-    if (*buf) e->t_retired.push_back(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    const long long c = std::max(2 * n, floor_n);
-    YTA_HIP(hipMalloc((void **)buf, sizeof(T) * (size_t)c));
-    *cap = c;
-    return YTA_OK;
-}
-
 int update_tensors(yta_bytetrack *e, void *caller_stream, const void *d_dets, int dtype,
                    long long row_stride, const int *det_counts, const float *d_feats,
                    long long feat_stride, const double *d_warps, const int *d_active,
                    const long long *next_id, double *d_rows, long long rows_capacity,
                    int *d_row_offsets, int *d_row_stream) {
-    YTA_CHECK(e && det_counts && d_row_offsets, YTA_ERR_INVALID, "null argument");
-    YTA_CHECK(dtype == YTA_F64 || dtype == YTA_F32 || dtype == YTA_F16, YTA_ERR_INVALID,
-              "dtype %d is none of YTA_F64, YTA_F32, YTA_F16", dtype);
-    YTA_CHECK(row_stride >= 6, YTA_ERR_INVALID, "row_stride %lld < 6", row_stride);
+    long long total = 0;
+    int rc = tensor_check_args(e, e ? e->S : 0, e ? e->a.D : 0, d_dets, dtype, row_stride,
+                               det_counts, d_feats, feat_stride, d_rows, rows_capacity,
+                               d_row_offsets, &total);
+    if (rc) return rc;
     YTA_CHECK(e->pipe_count == 0, YTA_ERR_INVALID, "pipelined frames in flight: collect them first");
     const int S = e->S, D = e->a.D;
-    long long total = 0;
-    for (int s = 0; s < S; ++s) {
-        YTA_CHECK(det_counts[s] >= 0, YTA_ERR_INVALID, "det_counts[%d] is negative", s);
-        total += det_counts[s];
-    }
-    YTA_CHECK(total <= 0x7fffffffLL, YTA_ERR_INVALID, "%lld detections in one frame", total);
-    const size_t esz = dtype == YTA_F64 ? 8 : dtype == YTA_F32 ? 4 : 2;
-    YTA_CHECK(total == 0 || (d_dets && (uintptr_t)d_dets % esz == 0), YTA_ERR_INVALID,
-              "d_dets null or not aligned to its element size");
-    YTA_CHECK(rows_capacity >= total, YTA_ERR_CAPACITY,
-              "d_rows holds %lld rows, the call needs sum(det_counts) = %lld", rows_capacity, total);
-    YTA_CHECK(total == 0 || (d_rows && (uintptr_t)d_rows % 16 == 0), YTA_ERR_INVALID,
-              "d_rows null or not 16-byte aligned");
-    YTA_CHECK(D == 0 || total == 0 || (d_feats && feat_stride >= D), YTA_ERR_INVALID,
-              "d_feats null or feat_stride < feat_dim");
     YTA_HIP(hipSetDevice(e->device));
     const hipStream_t cs = (hipStream_t)caller_stream;
-    {   // the cross-stream waits must not end up in somebody's graph
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(cs, &st) != hipSuccess) (void)hipGetLastError();
-        YTA_CHECK(st == hipStreamCaptureStatusNone, YTA_ERR_INVALID, "caller_stream is capturing");
-    }
-    int rc = tensor_capacity(e, det_counts);
+    rc = frame_refuse_capture(cs);
+    if (rc) return rc;
+    rc = tensor_capacity(e, det_counts);
     if (rc) return rc;
     // float64 rows of 6, 16-byte aligned as the kernels' loads need: read where they are
     const bool in_place = dtype == YTA_F64 && row_stride == 6 && (uintptr_t)d_dets % 16 == 0;
-    if (!e->t_off) YTA_HIP(hipMalloc((void **)&e->t_off, sizeof(int) * (S + 1)));
-    rc = tensor_stage(e, &e->t_det, &e->t_det_cap, in_place ? 0 : 6 * total, 6 * 1024);
+    if (!e->t_off) {
+        YTA_HIP(hipMalloc((void **)&e->t_off, sizeof(int) * (S + 1)));
+        e->t_ring.slot_bytes = bt_slot_bytes(S);
+        e->t_ring.host_waits = &e->tstat[TS_HOST_WAITS];
+    }
+    rc = tensor_stage(e->t_retired, &e->t_det, &e->t_det_cap, in_place ? 0 : 6 * total, 6 * 1024);
     if (rc) return rc;
     const bool gather = D > 0 && total > 0 && feat_stride != D;
     if (gather) {
-        rc = tensor_stage(e, &e->t_feat, &e->t_feat_cap, total * D, 1024LL * D);
+        rc = tensor_stage(e->t_retired, &e->t_feat, &e->t_feat_cap, total * D, 1024LL * D);
         if (rc) return rc;
     }
-    yta_bytetrack::TSlot *p = nullptr;
-    rc = tensor_slot_acquire(e, &p);
+    FrameSlot *p = nullptr;
+    rc = e->t_ring.acquire(&p);
     if (rc) return rc;
-    memcpy(p->h_counts, det_counts, sizeof(int) * S);
-    if (next_id) memcpy(p->h_nid, next_id, sizeof(long long) * S);
-    for (int s = 0; s < S; ++s) e->t_cum[s] += det_counts[s];
-    p->cum_at = e->t_cum;
-    p->seq = ++e->t_seq;
-    p->gen = e->t_gen;
-    e->t_dirty = true;
+    const BtSlotView hv = bt_slot_view(p->h, S), mv = bt_slot_view(p->m, S);
+    memcpy(hv.counts, det_counts, sizeof(int) * S);
+    if (next_id) memcpy(hv.nid, next_id, sizeof(long long) * S);
+    e->t_bound.enqueue(p, det_counts);
     ++e->tstat[TS_FRAMES];
     if (in_place) ++e->tstat[TS_INGEST_SKIPPED];
-    // the engine stream after everything queued on the caller's so far
-    YTA_HIP(hipEventRecord(p->in, cs));
-    YTA_HIP(hipStreamWaitEvent(e->stream, p->in, 0));
-    {
-        const long long rows = in_place ? 0 : total;
-        const unsigned grid = 1u + (unsigned)std::min<long long>(4096, (rows * 3 + ING_T - 1) / ING_T);
-        const long long *nid = next_id ? p->m_nid : nullptr;
-        if (dtype == YTA_F64)
-            hipLaunchKernelGGL(k_ingest<double>, dim3(grid), dim3(ING_T), 0, e->stream,
-                               (const double *)d_dets, row_stride, rows, e->t_det, p->m_counts, nid,
-                               S, e->t_off, e->a.cnt);
-        else if (dtype == YTA_F32)
-            hipLaunchKernelGGL(k_ingest<float>, dim3(grid), dim3(ING_T), 0, e->stream,
-                               (const float *)d_dets, row_stride, rows, e->t_det, p->m_counts, nid,
-                               S, e->t_off, e->a.cnt);
-        else
-            hipLaunchKernelGGL(k_ingest<_Float16>, dim3(grid), dim3(ING_T), 0, e->stream,
-                               (const _Float16 *)d_dets, row_stride, rows, e->t_det, p->m_counts,
-                               nid, S, e->t_off, e->a.cnt);
-        YTA_HIP(hipGetLastError());
-    }
+    rc = frame_hand_in(p, cs, e->stream);
+    if (rc) return rc;
+    rc = tensor_ingest(e->stream, d_dets, dtype, row_stride, in_place ? 0 : total, e->t_det,
+                       mv.counts, next_id ? mv.nid : nullptr, nullptr, S, e->t_off, e->a.cnt,
+                       nullptr);
+    if (rc) return rc;
     if (gather)
         YTA_HIP(hipMemcpy2DAsync(e->t_feat, sizeof(float) * D, d_feats, sizeof(float) * feat_stride,
                                  sizeof(float) * D, (size_t)total, hipMemcpyDeviceToDevice,
@@ -4505,16 +4294,14 @@ int update_tensors(yta_bytetrack *e, void *caller_stream, const void *d_dets, in
     e->a.active = nullptr;
     if (e->variant == VAR_BOTSORT) e->a.warp = e->d_warp_id;
     if (rc) return rc;
-    hipLaunchKernelGGL(k_out_offsets_scan, dim3(1), dim3(OFFS_T), 0, e->stream, e->a.cnt, S, e->CAP,
-                       d_row_offsets, (int *)nullptr);
-    hipLaunchKernelGGL(k_pack_rows, dim3(S), dim3(256), 0, e->stream, e->out_own, (long long)e->CAP,
-                       e->a.cnt, S, d_row_offsets, d_rows, rows_capacity, d_row_stream, p->m_live);
+    hipLaunchKernelGGL(k_tp_out_offsets<CountersNOut<BtCounters>>, dim3(1), dim3(TP_OFFS_T), 0,
+                       e->stream, CountersNOut<BtCounters>{e->a.cnt}, S, e->CAP, d_row_offsets,
+                       (int *)nullptr);
+    hipLaunchKernelGGL(k_tp_pack_rows<BtLive>, dim3(S), dim3(256), 0, e->stream, e->out_own,
+                       (long long)e->CAP, S, d_row_offsets, d_rows, rows_capacity, d_row_stream,
+                       BtLive{e->a.cnt, mv.live});
     YTA_HIP(hipGetLastError());
-    // the caller's stream after the frame's last launch: its later work sees the outputs and may
-    // free or overwrite the inputs
-    YTA_HIP(hipEventRecord(p->done, e->stream));
-    YTA_HIP(hipStreamWaitEvent(cs, p->done, 0));
-    return YTA_OK;
+    return frame_hand_back(p, cs, e->stream);
 }
 
 }  // namespace
@@ -4577,7 +4364,10 @@ int yta_bytetrack_destroy(yta_bytetrack *e) {
     if (e->d_det32) (void)hipFree(e->d_det32);
     if (e->h_det32) (void)hipHostFree(e->h_det32);
     pipe_free(e);
-    tensor_free(e);   // the engine stream was drained above: no tensor frame is in flight
+    e->t_ring.release();   // the engine stream was drained above: no tensor frame is in flight
+    tensor_free_retired(e->t_retired);
+    for (void *d : {(void *)e->t_det, (void *)e->t_off, (void *)e->t_feat})
+        if (d) (void)hipFree(d);
     for (hipEvent_t h : e->ev) (void)hipEventDestroy(h);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;

@@ -1544,7 +1544,7 @@ int yta_sof_apply_tensors(yta_sof *e, void *caller_stream, const void *const *fr
         rc = sof_grow(e, mh, mw);
         if (rc) return rc;
     }
-    CmcSlot *slot = nullptr;
+    FrameSlot *slot = nullptr;
     rc = cmc_hand_in(e->t, S, cs, e->stream, frames, frame_hw, frame_pitch, det_counts, &slot);
     if (rc) return rc;
     SofArgs &a = e->a;
@@ -1562,7 +1562,7 @@ int yta_sof_apply_tensors(yta_sof *e, void *caller_stream, const void *const *fr
     a.warps = d_warps;
     rc = sof_launch(e);
     if (rc) return rc;
-    return cmc_hand_back(slot, cs, e->stream);
+    return frame_hand_back(slot, cs, e->stream);
 }
 
 int yta_sof_tensor_stats(yta_sof *e, long long *out, int n) {

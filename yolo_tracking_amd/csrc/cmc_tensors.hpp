@@ -1,19 +1,17 @@
 // Tensor path of the camera-motion engines (yta_sof_apply_tensors in cmc.hip, yta_ecc_apply_tensors
 // in ecc.hip): the frames are S device tensors read where they are, addressed through a pointer
 // table (frame s = its first pixel's address, its h x w and its row pitch in bytes), and the call
-// is stream-ordered against the caller's stream with no host wait.  Written once for the two
-// engines: the ring of page-locked slots that carries a call's host arrays, the hand-off between
-// the caller's stream and the engine's, the one-block kernel that brings the arrays into HBM, and
-// the typed read of a detection row.  The protocol is the trackers' (bytetrack.hip and
-// oc_host.hpp keep their own copies, which also carry counters these engines do not have).
+// is stream-ordered against the caller's stream with no host wait.  The protocol (slots, hand-off)
+// is tensor_path.hpp's; here is what the two engines add to it: a slot's payload, the one-block
+// kernel that brings it into HBM, the checks of the frame table and the typed read of a detection
+// row.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <new>
-#include <vector>
 
 #include "common.hpp"
+#include "tensor_path.hpp"
 
 namespace yta {
 namespace cmc {
@@ -26,22 +24,12 @@ __device__ __forceinline__ double det_el(const void *rows, int dtype, long long 
                               : (double)static_cast<const _Float16 *>(rows)[i];
 }
 
-// A call's host arrays, in mapped page-locked memory the engine's first launch reads: S frame
-// addresses, S pitches, S x (h, w), S detection counts (SparseOptFlow only).
-struct CmcSlot {
-    hipEvent_t in = nullptr, done = nullptr;
-    void *h = nullptr, *m = nullptr;   // host / device view of the one allocation
-    long long seq = -1;                // enqueue order; -1: never used
-};
-
 enum { CTS_FRAMES, CTS_HOST_WAITS, CTS_N };
-constexpr size_t CMC_RING_MAX = 64;   // frames in flight before a call waits for the oldest
 constexpr int CMC_ING_T = 256;
 
 struct CmcTensors {
-    std::vector<CmcSlot *> ring;
+    FrameRing ring;
     long long stat[CTS_N] = {};   // frames enqueued; calls that blocked on the device
-    long long seq = 0;
     // the call's arrays in HBM (k_cmc_ingest), read by the engine's kernels; one set serves every
     // frame in flight, since the engine's stream runs them in order
     const uint8_t **ptr = nullptr;   // [S]
@@ -50,6 +38,8 @@ struct CmcTensors {
     int *off = nullptr;              // [S + 1] detection offsets
 };
 
+// A slot's block, which the engine's first launch reads: a call's host arrays, S frame addresses,
+// S pitches, S x (h, w), S detection counts (SparseOptFlow only).
 inline size_t cmc_slot_bytes(size_t S) { return S * (8 + 8 + 8 + 4); }
 struct CmcSlotView {
     const uint8_t **ptr;
@@ -80,15 +70,7 @@ __global__ __launch_bounds__(CMC_ING_T) void k_cmc_ingest(CmcSlotView in, int S,
         if (COUNTS) sum += max(in.counts[s], 0);
     }
     if (!COUNTS) return;
-    part[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < CMC_ING_T; d <<= 1) {   // inclusive Hillis-Steele scan
-        const int v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int r = part[t] - sum;   // exclusive prefix of this thread's run
+    int r = block_run_scan<CMC_ING_T>(sum, part);
     if (t == 0) off[0] = 0;
     for (int s = s0; s < s1; ++s) {
         r += max(in.counts[s], 0);
@@ -97,13 +79,7 @@ __global__ __launch_bounds__(CMC_ING_T) void k_cmc_ingest(CmcSlotView in, int S,
 }
 
 inline void cmc_tensors_free(CmcTensors &t) {
-    for (CmcSlot *p : t.ring) {
-        if (p->in) (void)hipEventDestroy(p->in);
-        if (p->done) (void)hipEventDestroy(p->done);
-        if (p->h) (void)hipHostFree(p->h);
-        delete p;
-    }
-    t.ring.clear();
+    t.ring.release();
     for (void *d : {(void *)t.ptr, (void *)t.pitch, (void *)t.hw, (void *)t.off})
         if (d) (void)hipFree(d);
     t.ptr = nullptr;
@@ -112,44 +88,7 @@ inline void cmc_tensors_free(CmcTensors &t) {
     t.off = nullptr;
 }
 
-inline bool cmc_slot_done(CmcSlot *p) {
-    if (p->seq < 0) return true;
-    if (hipEventQuery(p->done) == hipSuccess) return true;
-    (void)hipGetLastError();   // hipErrorNotReady
-    return false;
-}
-
-// A slot no queued frame reads: one whose frame has run, else a new one; with CMC_RING_MAX frames
-// in flight the call waits for the oldest (counted).
-inline int cmc_slot_acquire(CmcTensors &t, size_t S, CmcSlot **out) {
-    CmcSlot *oldest = nullptr;
-    for (CmcSlot *p : t.ring) {
-        if (!p->m) continue;   // its allocation failed part way
-        if (cmc_slot_done(p)) {
-            *out = p;
-            return YTA_OK;
-        }
-        if (!oldest || p->seq < oldest->seq) oldest = p;
-    }
-    if (t.ring.size() >= CMC_RING_MAX && oldest) {
-        ++t.stat[CTS_HOST_WAITS];
-        YTA_HIP(hipEventSynchronize(oldest->done));
-        *out = oldest;
-        return YTA_OK;
-    }
-    auto *p = new (std::nothrow) CmcSlot();
-    YTA_CHECK(p, YTA_ERR_NOMEM, "out of host memory");
-    t.ring.push_back(p);   // owned from here on (cmc_tensors_free)
-    YTA_HIP(hipEventCreateWithFlags(&p->in, hipEventDisableTiming));
-    YTA_HIP(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
-    YTA_HIP(hipHostMalloc(&p->h, cmc_slot_bytes(S), hipHostMallocMapped | hipHostMallocCoherent));
-    YTA_HIP(hipHostGetDevicePointer(&p->m, p->h, 0));
-    *out = p;
-    return YTA_OK;
-}
-
-// What both engines refuse before anything is enqueued.  The cross-stream waits must not end up
-// in somebody's graph, so a capturing caller stream is refused.
+// What both engines refuse before anything is enqueued (a capturing caller stream last).
 inline int cmc_check_frames(int S, hipStream_t cs, const void *const *frames, const int *frame_hw,
                             const long long *frame_pitch) {
     YTA_CHECK(frames && frame_hw && frame_pitch, YTA_ERR_INVALID, "null argument");
@@ -161,35 +100,33 @@ inline int cmc_check_frames(int S, hipStream_t cs, const void *const *frames, co
                   YTA_ERR_INVALID, "stream %d: pitch %lld outside 3 * w = %lld .. 2^31 - 1", s,
                   frame_pitch[s], 3LL * w);
     }
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(cs, &st) != hipSuccess) (void)hipGetLastError();
-    YTA_CHECK(st == hipStreamCaptureStatusNone, YTA_ERR_INVALID, "caller_stream is capturing");
-    return YTA_OK;
+    return frame_refuse_capture(cs);
 }
 
 // Take a slot, copy the call's host arrays into it (reusable by the caller at once), order the
 // engine's stream after everything queued on the caller's so far, and bring the arrays into HBM.
 inline int cmc_hand_in(CmcTensors &t, int S, hipStream_t cs, hipStream_t es,
                        const void *const *frames, const int *frame_hw,
-                       const long long *frame_pitch, const int *det_counts, CmcSlot **slot) {
+                       const long long *frame_pitch, const int *det_counts, FrameSlot **slot) {
     if (!t.ptr) {
+        t.ring.slot_bytes = cmc_slot_bytes((size_t)S);
+        t.ring.host_waits = &t.stat[CTS_HOST_WAITS];
         YTA_HIP(hipMalloc((void **)&t.ptr, sizeof(void *) * S));
         YTA_HIP(hipMalloc((void **)&t.pitch, sizeof(long long) * S));
         YTA_HIP(hipMalloc((void **)&t.hw, sizeof(int) * 2 * S));
         YTA_HIP(hipMalloc((void **)&t.off, sizeof(int) * (S + 1)));
     }
-    CmcSlot *p = nullptr;
-    int rc = cmc_slot_acquire(t, (size_t)S, &p);
+    FrameSlot *p = nullptr;
+    int rc = t.ring.acquire(&p);
     if (rc) return rc;
     const CmcSlotView hv = cmc_slot_view(p->h, (size_t)S);
     memcpy(hv.ptr, frames, sizeof(void *) * S);
     memcpy(hv.pitch, frame_pitch, sizeof(long long) * S);
     memcpy(hv.hw, frame_hw, sizeof(int) * 2 * S);
     if (det_counts) memcpy(hv.counts, det_counts, sizeof(int) * S);
-    p->seq = ++t.seq;
     ++t.stat[CTS_FRAMES];
-    YTA_HIP(hipEventRecord(p->in, cs));
-    YTA_HIP(hipStreamWaitEvent(es, p->in, 0));
+    rc = frame_hand_in(p, cs, es);
+    if (rc) return rc;
     const CmcSlotView mv = cmc_slot_view(p->m, (size_t)S);
     if (det_counts)
         hipLaunchKernelGGL(k_cmc_ingest<true>, dim3(1), dim3(CMC_ING_T), 0, es, mv, S, t.ptr,
@@ -199,14 +136,6 @@ inline int cmc_hand_in(CmcTensors &t, int S, hipStream_t cs, hipStream_t es,
                            t.pitch, t.hw, t.off);
     YTA_HIP(hipGetLastError());
     *slot = p;
-    return YTA_OK;
-}
-
-// The caller's stream after the frame's last launch: its later work sees the outputs and may free
-// or overwrite the inputs.
-inline int cmc_hand_back(CmcSlot *p, hipStream_t cs, hipStream_t es) {
-    YTA_HIP(hipEventRecord(p->done, es));
-    YTA_HIP(hipStreamWaitEvent(cs, p->done, 0));
     return YTA_OK;
 }
 

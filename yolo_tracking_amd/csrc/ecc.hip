@@ -1029,7 +1029,7 @@ int yta_ecc_apply_tensors(yta_ecc *e, void *caller_stream, const void *const *fr
         rc = ecc_grow(e, mh, mw);
         if (rc) return rc;
     }
-    CmcSlot *slot = nullptr;
+    FrameSlot *slot = nullptr;
     rc = cmc_hand_in(e->t, S, cs, e->stream, frames, frame_hw, frame_pitch, nullptr, &slot);
     if (rc) return rc;
     EccArgs &a = e->a;
@@ -1041,7 +1041,7 @@ int yta_ecc_apply_tensors(yta_ecc *e, void *caller_stream, const void *const *fr
     a.warps = d_warps;
     rc = ecc_launch(e);
     if (rc) return rc;
-    return cmc_hand_back(slot, cs, e->stream);
+    return frame_hand_back(slot, cs, e->stream);
 }
 
 int yta_ecc_tensor_stats(yta_ecc *e, long long *out, int n) {

@@ -1,5 +1,5 @@
-// Host side shared by the engines (the only device code is oc_tensors.hpp's, launched by the
-// family's tensor path at the end of this file).
+// Host side shared by the engines (no device code but two accessors of tensor_path.hpp's kernels,
+// which the family's tensor path at the end of this file launches).
 //
 // For every engine: dalloc / DALLOC (tracked device allocations) and grow_pair (a device buffer
 // with its page-locked twin).
@@ -24,9 +24,9 @@
 #include <vector>
 
 #include "common.hpp"
-#include "oc_tensors.hpp"
 #include "ocsort_common.hpp"
 #include "subset.hpp"
+#include "tensor_path.hpp"
 
 namespace yta {
 
@@ -105,32 +105,33 @@ struct OcSized {
     }
 };
 
-// The tensor path's host state (oc_update_tensors below): device rows in and out, nothing waited
-// for.  A ring of slots, one per frame in flight: two events and page-locked mapped staging.
-struct OcTensorSlot {
-    hipEvent_t in = nullptr, done = nullptr;
-    int *h_counts = nullptr, *m_counts = nullptr;      // S detection counts in (host / device view)
-    long long *h_nid = nullptr, *m_nid = nullptr;      // S ID counters in
-    int *h_wh = nullptr, *m_wh = nullptr;              // S x (w, h) image sizes in
-    int *h_live = nullptr, *m_live = nullptr;          // S live tracker counts back (k_oc_pack_rows)
-    std::vector<long long> cum_at;                     // t.cum when the frame was enqueued
-    long long seq = -1, gen = -1;                      // enqueue order; the t.gen it belongs to
+// The tensor path's host state (oc_update_tensors below, protocol: tensor_path.hpp).  A slot
+// (oc_slot_view) carries the call's counts, ID counters and image sizes in and the streams' live
+// tracker counts back.
+struct OcSlotView {
+    long long *nid;   // S ID counters in
+    int *counts;      // S detection counts in
+    int *wh;          // S x (w, h) image sizes in
+    int *live;        // S live tracker counts back (k_tp_pack_rows)
 };
+inline size_t oc_slot_bytes(size_t S) { return S * (8 + 4 + 8 + 4); }
+inline OcSlotView oc_slot_view(void *base, size_t S) {
+    long long *nid = static_cast<long long *>(base);
+    int *counts = reinterpret_cast<int *>(nid + S);
+    return {nid, counts, counts + S, counts + 3 * S};
+}
 struct OcTensorState {
-    std::vector<OcTensorSlot *> ring;
-    double *det = nullptr;               // float64 staging rows (k_oc_ingest)
+    FrameRing ring;
+    TrackBound bound;                    // live tracks: h_cnt's n_trk
+    double *det = nullptr;               // float64 staging rows (k_tp_ingest)
     long long det_cap = 0;
-    int *off = nullptr;                  // S + 1 detection offsets (k_oc_ingest)
-    int *wh = nullptr;                   // S x (w, h) on the device (k_oc_ingest)
+    int *off = nullptr;                  // S + 1 detection offsets (k_tp_ingest)
+    int *wh = nullptr;                   // S x (w, h) on the device (k_tp_ingest)
     float *feat = nullptr;               // feature rows gathered from a strided tensor
     long long feat_cap = 0;
     std::vector<void *> retired;         // outgrown staging a queued frame may still read: freed
                                          // at the next host wait
     long long stat[4] = {};              // frames, host_waits, reserves, ingest_skipped
-    std::vector<long long> cum, base_cum, base_live;   // per stream: detections enqueued so far;
-                                                       // cum and n_trk when h_cnt was last exact
-    bool dirty = false;                  // tensor frames enqueued since h_cnt was last read
-    long long seq = 0, gen = 0;          // gen: bumped whenever h_cnt is made exact again
 };
 
 template <typename BufT, typename ParamsT>
@@ -164,10 +165,8 @@ int oc_read_counters(E *e) {
     YTA_HIP(host_wait(e->stream));
     // every tensor frame enqueued so far has run: h_cnt is exact again, and nothing reads the
     // staging those frames outgrew
-    e->t.dirty = false;
-    ++e->t.gen;
-    for (void *p : e->t.retired) (void)hipFree(p);
-    e->t.retired.clear();
+    e->t.bound.exact();
+    tensor_free_retired(e->t.retired);
     return YTA_OK;
 }
 
@@ -175,7 +174,7 @@ int oc_read_counters(E *e) {
 // up to date, for the entry points that size or report from it.
 template <typename E>
 int oc_catch_up(E *e) {
-    if (!e->t.dirty) return YTA_OK;
+    if (!e->t.bound.dirty) return YTA_OK;
     YTA_HIP(hipSetDevice(e->device));
     return oc_read_counters(e);
 }
@@ -361,140 +360,48 @@ int oc_end_frame(E *e, long long *next_id, double *out, int out_capacity, int *o
 }
 
 // ------------------------------------------------------------------ the tensor path
-// yta_<t>_update_tensors: device rows in, device rows out, stream-ordered.  The caller's stream
-// hands over to the engine's stream through an event, the frame runs there as plain launches
-// (k_oc_ingest, the engine's kernels, k_oc_out_offsets, k_oc_pack_rows), and a second event hands
-// back: nothing is waited for on the host unless the capacity bound below fails.
+// yta_<t>_update_tensors: device rows in, device rows out, stream-ordered.  The protocol is
+// tensor_path.hpp's: the frame runs on the engine's stream as plain launches (k_tp_ingest, the
+// engine's kernels, k_tp_out_offsets, k_tp_pack_rows), and nothing is waited for on the host unless
+// the capacity bound below fails.
 enum { OTS_FRAMES, OTS_HOST_WAITS, OTS_RESERVES, OTS_INGEST_SKIPPED, OTS_N };
-constexpr size_t OC_RING_MAX = 64;   // frames in flight before a call waits for the oldest
 
-template <typename E>
-void oc_tensor_free(E *e) {
-    OcTensorState &t = e->t;
-    for (OcTensorSlot *p : t.ring) {
-        if (p->in) (void)hipEventDestroy(p->in);
-        if (p->done) (void)hipEventDestroy(p->done);
-        for (void *h : {(void *)p->h_counts, (void *)p->h_nid, (void *)p->h_wh, (void *)p->h_live})
-            if (h) (void)hipHostFree(h);
-        delete p;
-    }
-    t.ring.clear();
-    for (void *d : {(void *)t.det, (void *)t.off, (void *)t.wh, (void *)t.feat})
-        if (d) (void)hipFree(d);
-    for (void *d : t.retired) (void)hipFree(d);
-    t.retired.clear();
-    t.det = nullptr;
-    t.off = nullptr;
-    t.wh = nullptr;
-    t.feat = nullptr;
-}
-
-inline int oc_tensor_slot_new(OcTensorState &t, size_t S, OcTensorSlot **out) {
-    auto *p = new (std::nothrow) OcTensorSlot();
-    YTA_CHECK(p, YTA_ERR_NOMEM, "out of host memory");
-    t.ring.push_back(p);   // owned from here on (oc_tensor_free)
-    const unsigned mf = hipHostMallocMapped | hipHostMallocCoherent;
-    YTA_HIP(hipEventCreateWithFlags(&p->in, hipEventDisableTiming));
-    YTA_HIP(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
-    YTA_HIP(hipHostMalloc((void **)&p->h_counts, sizeof(int) * S, mf));
-    YTA_HIP(hipHostMalloc((void **)&p->h_nid, sizeof(long long) * S, mf));
-    YTA_HIP(hipHostMalloc((void **)&p->h_wh, sizeof(int) * 2 * S, mf));
-    YTA_HIP(hipHostMalloc((void **)&p->h_live, sizeof(int) * S, mf));
-    YTA_HIP(hipHostGetDevicePointer((void **)&p->m_counts, p->h_counts, 0));
-    YTA_HIP(hipHostGetDevicePointer((void **)&p->m_nid, p->h_nid, 0));
-    YTA_HIP(hipHostGetDevicePointer((void **)&p->m_wh, p->h_wh, 0));
-    YTA_HIP(hipHostGetDevicePointer((void **)&p->m_live, p->h_live, 0));
-    p->cum_at.assign(S, 0);
-    *out = p;
-    return YTA_OK;
-}
-
-inline bool oc_tensor_slot_done(OcTensorSlot *p) {
-    if (p->seq < 0) return true;   // never used
-    if (hipEventQuery(p->done) == hipSuccess) return true;
-    (void)hipGetLastError();   // hipErrorNotReady
-    return false;
-}
-
-// A slot no queued frame reads: one whose frame has run, else a new one; with OC_RING_MAX frames
-// in flight the call waits for the oldest.
-inline int oc_tensor_slot_acquire(OcTensorState &t, size_t S, OcTensorSlot **out) {
-    OcTensorSlot *oldest = nullptr;
-    for (OcTensorSlot *p : t.ring) {
-        if (!p->m_live) continue;   // its allocation failed part way
-        if (oc_tensor_slot_done(p)) {
-            *out = p;
-            return YTA_OK;
-        }
-        if (!oldest || p->seq < oldest->seq) oldest = p;
-    }
-    if (t.ring.size() < OC_RING_MAX || !oldest) return oc_tensor_slot_new(t, S, out);
-    ++t.stat[OTS_HOST_WAITS];
-    YTA_HIP(hipEventSynchronize(oldest->done));
-    *out = oldest;
-    return YTA_OK;
-}
+// k_tp_pack_rows' accessor: a stream's live trackers after the frame into the slot.
+template <typename C>
+struct OcLive {
+    const C *cnt;
+    int *live;
+    __device__ void operator()(int s) const { live[s] = cnt[s].n_trk; }
+};
 
 // Capacity before anything is enqueued.  max_dets from the frame's counts.  Track capacity as
 // oc_begin_frame bounds it (births are appended before removals, so a stream's list never holds
-// more than n_trk + m): its trackers after this frame are at most its live trackers after some
-// earlier frame plus every detection enqueued for it since, this frame's included.  The earlier
-// frame is the newest tensor frame whose event has completed (k_oc_pack_rows stored its n_trk
-// into the slot), else the last exact h_cnt.  Only a bound that does not fit waits for the engine
+// more than n_trk + m), through TrackBound.  Only a bound that does not fit waits for the engine
 // stream and reads the exact counters; only an exact need that does not fit grows the engine, by
 // oc_begin_frame's geometric rule.
 template <typename E>
 int oc_tensor_capacity(E *e, const int *counts) {
     OcTensorState &t = e->t;
     const int S = e->S, CAP = e->b.a.CAP, MAXD = e->b.a.MAXD;
-    auto rebase = [&] {   // h_cnt is exact: later frames are bounded from it
-        t.base_live.resize(S);
-        for (int s = 0; s < S; ++s) t.base_live[s] = e->b.h_cnt[s].n_trk;
-        t.base_cum = t.cum;
-    };
-    if (t.cum.empty()) t.cum.assign(S, 0);
-    if (!t.dirty) rebase();
+    auto rebase = [&] { t.bound.rebase(S, [&](int s) { return e->b.h_cnt[s].n_trk; }); };
+    if (!t.bound.dirty) rebase();
     int need_d = MAXD;
     for (int s = 0; s < S; ++s) need_d = std::max(need_d, counts[s]);
-    bool fits = need_d <= MAXD;
-    if (fits) {
-        const OcTensorSlot *k0 = nullptr;
-        for (OcTensorSlot *p : t.ring)
-            if (p->seq >= 0 && p->gen == t.gen && (!k0 || p->seq > k0->seq) &&
-                oc_tensor_slot_done(p))
-                k0 = p;
-        for (int s = 0; s < S && fits; ++s) {
-            const long long live = k0 ? (long long)k0->h_live[s] : t.base_live[s];
-            const long long since = t.cum[s] - (k0 ? k0->cum_at[s] : t.base_cum[s]);
-            fits = live + since + counts[s] <= CAP;
-        }
-    }
-    if (fits) return YTA_OK;
+    if (need_d <= MAXD && t.bound.fits(t.ring, counts, CAP, [S](void *h, int s) {
+            return oc_slot_view(h, S).live[s];
+        }))
+        return YTA_OK;
     ++t.stat[OTS_HOST_WAITS];
     int rc = oc_read_counters(e);
     if (rc) return rc;
     rebase();
     int need_c = CAP;
     for (int s = 0; s < S; ++s)
-        need_c = (int)std::max<long long>(need_c, t.base_live[s] + counts[s]);
+        need_c = (int)std::max<long long>(need_c, t.bound.base_live[s] + counts[s]);
     if (need_d <= MAXD && need_c <= CAP) return YTA_OK;
     ++t.stat[OTS_RESERVES];
     return oc_reserve(e, need_c > CAP ? std::max(need_c, 2 * CAP) : CAP,
                       need_d > MAXD ? std::max(need_d, 2 * MAXD) : MAXD);
-}
-
-// Device staging of at least n elements; an outgrown buffer is kept until the next host wait (a
-// queued frame may still read it).
-template <typename T>
-int oc_tensor_stage(OcTensorState &t, T **buf, long long *cap, long long n, long long floor_n) {
-    if (n <= *cap && *buf) return YTA_OK;
-    if (*buf) t.retired.push_back(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    const long long c = std::max(2 * n, floor_n);
-    YTA_HIP(hipMalloc((void **)buf, sizeof(T) * (size_t)c));
-    *cap = c;
-    return YTA_OK;
 }
 
 // launch(d_dets, d_off, d_feats, d_wh): the engine's frame on e->stream from packed float64 rows,
@@ -507,86 +414,51 @@ int oc_update_tensors(E *e, void *caller_stream, const void *d_dets, int dtype,
                       const long long *next_id, double *d_rows, long long rows_capacity,
                       int *d_row_offsets, int *d_row_stream, Launch launch) {
     using Counters = typename E::Buf::Counters;
-    YTA_CHECK(e && det_counts && d_row_offsets, YTA_ERR_INVALID, "null argument");
-    YTA_CHECK(dtype == YTA_F64 || dtype == YTA_F32 || dtype == YTA_F16, YTA_ERR_INVALID,
-              "dtype %d is none of YTA_F64, YTA_F32, YTA_F16", dtype);
-    YTA_CHECK(row_stride >= 6, YTA_ERR_INVALID, "row_stride %lld < 6", row_stride);
+    long long total = 0;
+    int rc = tensor_check_args(e, e ? e->S : 0, e ? e->D : 0, d_dets, dtype, row_stride,
+                               det_counts, d_feats, feat_stride, d_rows, rows_capacity,
+                               d_row_offsets, &total);
+    if (rc) return rc;
     YTA_CHECK(img_wh || e->prm.asso_func != 4, YTA_ERR_INVALID, "centroid needs img_wh");
     const int S = e->S, D = e->D;
-    long long total = 0;
-    for (int s = 0; s < S; ++s) {
-        YTA_CHECK(det_counts[s] >= 0, YTA_ERR_INVALID, "det_counts[%d] is negative", s);
-        total += det_counts[s];
-    }
-    YTA_CHECK(total <= 0x7fffffffLL, YTA_ERR_INVALID, "%lld detections in one frame", total);
-    const size_t esz = dtype == YTA_F64 ? 8 : dtype == YTA_F32 ? 4 : 2;
-    YTA_CHECK(total == 0 || (d_dets && (uintptr_t)d_dets % esz == 0), YTA_ERR_INVALID,
-              "d_dets null or not aligned to its element size");
-    YTA_CHECK(rows_capacity >= total, YTA_ERR_CAPACITY,
-              "d_rows holds %lld rows, the call needs sum(det_counts) = %lld", rows_capacity, total);
-    YTA_CHECK(total == 0 || (d_rows && (uintptr_t)d_rows % 16 == 0), YTA_ERR_INVALID,
-              "d_rows null or not 16-byte aligned");
-    YTA_CHECK(D == 0 || total == 0 ||
-                  (d_feats && (uintptr_t)d_feats % sizeof(float) == 0 && feat_stride >= D),
-              YTA_ERR_INVALID, "d_feats null, misaligned or feat_stride < feat_dim");
     YTA_HIP(hipSetDevice(e->device));
     const hipStream_t cs = (hipStream_t)caller_stream;
-    {   // the cross-stream waits must not end up in somebody's graph
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(cs, &st) != hipSuccess) (void)hipGetLastError();
-        YTA_CHECK(st == hipStreamCaptureStatusNone, YTA_ERR_INVALID, "caller_stream is capturing");
-    }
-    int rc = oc_tensor_capacity(e, det_counts);
+    rc = frame_refuse_capture(cs);
+    if (rc) return rc;
+    rc = oc_tensor_capacity(e, det_counts);
     if (rc) return rc;
     OcTensorState &t = e->t;
     // float64 rows of 6, 16-byte aligned as the kernels' loads need: read where they are
     const bool in_place = dtype == YTA_F64 && row_stride == 6 && (uintptr_t)d_dets % 16 == 0;
-    if (!t.off) YTA_HIP(hipMalloc((void **)&t.off, sizeof(int) * (S + 1)));
+    if (!t.off) {
+        YTA_HIP(hipMalloc((void **)&t.off, sizeof(int) * (S + 1)));
+        t.ring.slot_bytes = oc_slot_bytes(S);
+        t.ring.host_waits = &t.stat[OTS_HOST_WAITS];
+    }
     if (!t.wh) YTA_HIP(hipMalloc((void **)&t.wh, sizeof(int) * 2 * S));
-    rc = oc_tensor_stage(t, &t.det, &t.det_cap, in_place ? 0 : 6 * total, 6 * 1024);
+    rc = tensor_stage(t.retired, &t.det, &t.det_cap, in_place ? 0 : 6 * total, 6 * 1024);
     if (rc) return rc;
     const bool gather = D > 0 && total > 0 && feat_stride != D;
     if (gather) {
-        rc = oc_tensor_stage(t, &t.feat, &t.feat_cap, total * D, 1024LL * D);
+        rc = tensor_stage(t.retired, &t.feat, &t.feat_cap, total * D, 1024LL * D);
         if (rc) return rc;
     }
-    OcTensorSlot *p = nullptr;
-    rc = oc_tensor_slot_acquire(t, S, &p);
+    FrameSlot *p = nullptr;
+    rc = t.ring.acquire(&p);
     if (rc) return rc;
-    memcpy(p->h_counts, det_counts, sizeof(int) * S);
-    if (next_id) memcpy(p->h_nid, next_id, sizeof(long long) * S);
-    if (img_wh) memcpy(p->h_wh, img_wh, sizeof(int) * 2 * S);
-    for (int s = 0; s < S; ++s) t.cum[s] += det_counts[s];
-    p->cum_at = t.cum;
-    p->seq = ++t.seq;
-    p->gen = t.gen;
-    t.dirty = true;
+    const OcSlotView hv = oc_slot_view(p->h, S), mv = oc_slot_view(p->m, S);
+    memcpy(hv.counts, det_counts, sizeof(int) * S);
+    if (next_id) memcpy(hv.nid, next_id, sizeof(long long) * S);
+    if (img_wh) memcpy(hv.wh, img_wh, sizeof(int) * 2 * S);
+    t.bound.enqueue(p, det_counts);
     ++t.stat[OTS_FRAMES];
     if (in_place) ++t.stat[OTS_INGEST_SKIPPED];
-    // the engine stream after everything queued on the caller's so far
-    YTA_HIP(hipEventRecord(p->in, cs));
-    YTA_HIP(hipStreamWaitEvent(e->stream, p->in, 0));
-    {
-        const long long rows = in_place ? 0 : total;
-        const unsigned grid =
-            1u + (unsigned)std::min<long long>(4096, (rows * 3 + OC_ING_T - 1) / OC_ING_T);
-        const long long *nid = next_id ? p->m_nid : nullptr;
-        const int *wh = img_wh ? p->m_wh : nullptr;
-        Counters *cnt = e->b.a.cnt;
-        if (dtype == YTA_F64)
-            hipLaunchKernelGGL((k_oc_ingest<double, Counters>), dim3(grid), dim3(OC_ING_T), 0,
-                               e->stream, (const double *)d_dets, row_stride, rows, t.det,
-                               p->m_counts, nid, wh, S, t.off, cnt, t.wh);
-        else if (dtype == YTA_F32)
-            hipLaunchKernelGGL((k_oc_ingest<float, Counters>), dim3(grid), dim3(OC_ING_T), 0,
-                               e->stream, (const float *)d_dets, row_stride, rows, t.det,
-                               p->m_counts, nid, wh, S, t.off, cnt, t.wh);
-        else
-            hipLaunchKernelGGL((k_oc_ingest<_Float16, Counters>), dim3(grid), dim3(OC_ING_T), 0,
-                               e->stream, (const _Float16 *)d_dets, row_stride, rows, t.det,
-                               p->m_counts, nid, wh, S, t.off, cnt, t.wh);
-        YTA_HIP(hipGetLastError());
-    }
+    rc = frame_hand_in(p, cs, e->stream);
+    if (rc) return rc;
+    rc = tensor_ingest(e->stream, d_dets, dtype, row_stride, in_place ? 0 : total, t.det,
+                       mv.counts, next_id ? mv.nid : nullptr, img_wh ? mv.wh : nullptr, S, t.off,
+                       e->b.a.cnt, t.wh);
+    if (rc) return rc;
     if (gather)
         YTA_HIP(hipMemcpy2DAsync(t.feat, sizeof(float) * D, d_feats, sizeof(float) * feat_stride,
                                  sizeof(float) * D, (size_t)total, hipMemcpyDeviceToDevice,
@@ -597,17 +469,14 @@ int oc_update_tensors(E *e, void *caller_stream, const void *d_dets, int dtype,
     e->mask.req_dev = nullptr;
     if (rc) return rc;
     const int CAP = e->b.a.CAP;
-    hipLaunchKernelGGL((k_oc_out_offsets<Counters>), dim3(1), dim3(OC_OFFS_T), 0, e->stream,
-                       e->b.a.cnt, S, CAP, d_row_offsets);
-    hipLaunchKernelGGL((k_oc_pack_rows<Counters>), dim3(S), dim3(256), 0, e->stream, e->b.out_own,
-                       (long long)CAP, e->b.a.cnt, S, d_row_offsets, d_rows, rows_capacity,
-                       d_row_stream, p->m_live);
+    hipLaunchKernelGGL(k_tp_out_offsets<CountersNOut<Counters>>, dim3(1), dim3(TP_OFFS_T), 0,
+                       e->stream, CountersNOut<Counters>{e->b.a.cnt}, S, CAP, d_row_offsets,
+                       (int *)nullptr);
+    hipLaunchKernelGGL(k_tp_pack_rows<OcLive<Counters>>, dim3(S), dim3(256), 0, e->stream,
+                       e->b.out_own, (long long)CAP, S, d_row_offsets, d_rows, rows_capacity,
+                       d_row_stream, OcLive<Counters>{e->b.a.cnt, mv.live});
     YTA_HIP(hipGetLastError());
-    // the caller's stream after the frame's last launch: its later work sees the outputs and may
-    // free or overwrite the inputs
-    YTA_HIP(hipEventRecord(p->done, e->stream));
-    YTA_HIP(hipStreamWaitEvent(cs, p->done, 0));
-    return YTA_OK;
+    return frame_hand_back(p, cs, e->stream);
 }
 
 template <typename E>
@@ -637,8 +506,7 @@ int oc_reset(E *e) {
     YTA_HIP(hipGetLastError());
     YTA_HIP(host_wait(e->stream));
     memset(e->b.h_cnt, 0, sizeof(typename E::Buf::Counters) * e->S);
-    e->t.dirty = false;   // exact again: every tensor frame has run and been wiped
-    ++e->t.gen;
+    e->t.bound.exact();   // exact again: every tensor frame has run and been wiped
     return YTA_OK;
 }
 
@@ -661,7 +529,10 @@ int oc_destroy(E *e) {
     if (e->stream) (void)host_wait(e->stream);
     e->b.release();
     e->mask.release();
-    oc_tensor_free(e);
+    e->t.ring.release();
+    tensor_free_retired(e->t.retired);
+    for (void *d : {(void *)e->t.det, (void *)e->t.off, (void *)e->t.wh, (void *)e->t.feat})
+        if (d) (void)hipFree(d);
     if (e->h_dets) (void)hipHostFree(e->h_dets);
     if (e->d_det_in) (void)hipFree(e->d_det_in);
     if (e->h_feat) (void)hipHostFree(e->h_feat);

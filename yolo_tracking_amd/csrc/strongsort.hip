@@ -29,10 +29,10 @@
 //                                per track
 // All six take an [S] mask (SsArgs::active; null: every stream): a masked stream's blocks return
 // before their first barrier and leave its state untouched (update_streams, update_device_masked,
-// update_tensors' `active`).  A tensor frame (yta_strongsort_update_tensors) wraps them in
-// ss_tensors.hpp's three: k_ss_ingest in front (counts, offsets, ID counters and the widened
-// detection rows; the feature rows stay where the caller has them, k_ss_norm reads them through
-// SsArgs::foff / fstride), k_ss_out_offsets and k_ss_pack_rows behind.
+// update_tensors' `active`).  A tensor frame (yta_strongsort_update_tensors, protocol:
+// tensor_path.hpp) wraps them in three: k_ss_ingest in front (counts, offsets, ID counters and the
+// widened detection rows; the feature rows stay where the caller has them, k_ss_norm reads them
+// through SsArgs::foff / fstride), k_tp_out_offsets and k_tp_pack_rows behind.
 //
 // Float32 order (the reference's np.dot / np.linalg.norm fix none; tests/strongsort_oracle.py
 // restates this one, device against restatement is bit-exact):
@@ -56,8 +56,8 @@
 
 #include "kf_xyah.hpp"
 #include "lsa_replay.hpp"
-#include "ss_tensors.hpp"
 #include "subset.hpp"
+#include "tensor_path.hpp"
 
 using namespace yta;
 
@@ -594,20 +594,74 @@ int lsa_lds_setup(const void *fn, size_t bytes) {
     return YTA_OK;
 }
 
-// The tensor path's host state (yta_strongsort_update_tensors): a ring of slots, one per frame in
-// flight.  A slot is two events and one page-locked mapped block: S counts and S + 1 offsets in,
-// S track counts back (k_ss_pack_rows), S ID counters in.
-struct SsTensorSlot {
-    hipEvent_t in = nullptr, done = nullptr;
-    void *h = nullptr;
-    int *h_counts = nullptr, *h_offs = nullptr, *h_live = nullptr;
-    long long *h_nid = nullptr;
-    int *m_counts = nullptr, *m_offs = nullptr, *m_live = nullptr;   // the device's view
-    long long *m_nid = nullptr;
-    long long seq = -1;   // enqueue order (-1: never used)
+// One launch for everything a tensor frame brings in, on StrongSORT's layout: fixed slabs
+// S x MAXD x 6 (the engine never grows) and plain int arrays for the counts.  The only kernel of a
+// frame that reads the call's slot (mapped host memory): `counts` (S) and `offs` (S + 1, their
+// prefix sums, taken on the host where the counts are checked against max_dets anyway) and `nid`
+// (S, null when the caller passed no ID counters).
+// Block 0 copies them to the device: ndet[s], off[0..S] and, for the streams the mask leaves
+// active, hdr[s][hdr_next].  The later kernels read only those.
+// Blocks 1..: block 1 + s * cps + c widens chunk c of stream s: the caller's rows offs[s] ..
+// offs[s + 1] (`stride` elements apart, of type T) exactly into the float64 slab rows
+// dets[s][0..m).  A thread takes two neighbouring columns of one row (6 is even, so a pair never
+// straddles rows) with two scalar loads, which any stride and any element alignment allow, and
+// one 16-B store: the slab is a device allocation and the pair starts at an even element, so the
+// store is 16-B aligned.  Bytes per detection: 6 * sizeof(T) read, 48 written; a block of a
+// stream that is masked out or has no rows left returns at once.
+constexpr int SS_ING_T = 256;
+template <typename T>
+__global__ __launch_bounds__(SS_ING_T) void k_ss_ingest(const T *src, long long stride,
+                                                        const int *counts, const int *offs,
+                                                        const long long *nid, const int *active,
+                                                        int S, int maxd, int cps, int *ndet,
+                                                        int *off, int *hdr, int hdr_n,
+                                                        int hdr_next, double *dets) {
+    const int t = threadIdx.x;
+    if (blockIdx.x == 0) {
+        for (int s = t; s < S; s += SS_ING_T) {
+            ndet[s] = counts[s];
+            off[s + 1] = offs[s + 1];
+            if (nid && (!active || active[s])) hdr[s * hdr_n + hdr_next] = (int)nid[s];
+        }
+        if (t == 0) off[0] = 0;
+        return;
+    }
+    const int b = blockIdx.x - 1, s = b / cps, c = b - s * cps;
+    if (active && !active[s]) return;
+    const int k = c * SS_ING_T + t, m = min(counts[s], maxd);
+    if (k >= 3 * m) return;
+    const int row = k / 3, cp = k - 3 * row;
+    const T *p = src + ((long long)offs[s] + row) * stride + 2 * cp;
+    double2 *d = reinterpret_cast<double2 *>(dets + ((long long)s * maxd + row) * 6);
+    d[cp] = make_double2((double)p[0], (double)p[1]);
+}
+
+// The accessors of tensor_path.hpp's kernels behind the frame: a stream's output count
+// (k_tp_out_offsets), and its track count after the frame stored into the slot (k_tp_pack_rows),
+// where n_tracks() reads it after the frame's event.
+struct SsNOut {
+    const int *nout;
+    __device__ int operator()(int s) const { return nout[s]; }
 };
+struct SsLive {
+    const int *ntrk;
+    int *live;
+    __device__ void operator()(int s) const { live[s] = ntrk[s]; }
+};
+
+// A tensor frame's slot block: S ID counters in (8-B aligned), then S counts and S + 1 offsets
+// in, S track counts back.
+struct SsSlotView {
+    long long *nid;
+    int *counts, *offs, *live;
+};
+size_t ss_slot_bytes(size_t S) { return sizeof(long long) * S + sizeof(int) * (3 * S + 1); }
+SsSlotView ss_slot_view(void *base, size_t S) {
+    long long *nid = static_cast<long long *>(base);
+    int *counts = reinterpret_cast<int *>(nid + S);
+    return {nid, counts, counts + S, counts + 2 * S + 1};
+}
 enum { STS_FRAMES, STS_HOST_WAITS, STS_RESERVES, STS_INGEST_SKIPPED, STS_N };
-constexpr size_t SS_RING_MAX = 64;   // frames in flight before a call waits for the oldest
 
 }  // namespace
 
@@ -624,18 +678,12 @@ struct yta_strongsort {
     size_t lds = 0;
     int ws_n = 0;
     StreamMask mask;        // stream-subset updates (subset.hpp)
-    std::vector<SsTensorSlot *> ring;
-    SsTensorSlot *newest = nullptr;   // the last tensor frame, while its counts are the newest
+    FrameRing ring;                   // the tensor path's slots (ss_slot_view)
+    FrameSlot *newest = nullptr;      // the last tensor frame, while its counts are the newest
     std::vector<int> ntrk;            // tracks per stream after the last update the host saw
     long long stat[STS_N] = {};
-    long long seq = 0;
     ~yta_strongsort() {
-        for (SsTensorSlot *p : ring) {
-            if (p->in) (void)hipEventDestroy(p->in);
-            if (p->done) (void)hipEventDestroy(p->done);
-            if (p->h) (void)hipHostFree(p->h);
-            delete p;
-        }
+        ring.release();
         mask.release();
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -690,10 +738,10 @@ int ss_check_err(yta_strongsort *e) {
 }
 
 // After a host wait on the engine's stream: the newest tensor frame's track counts (stored into
-// its slot by k_ss_pack_rows) become the host's.
+// its slot by k_tp_pack_rows) become the host's.
 void ss_take_live(yta_strongsort *e) {
     if (!e->newest) return;
-    memcpy(e->ntrk.data(), e->newest->h_live, sizeof(int) * e->a.S);
+    memcpy(e->ntrk.data(), ss_slot_view(e->newest->h, e->a.S).live, sizeof(int) * e->a.S);
     e->newest = nullptr;
 }
 
@@ -744,56 +792,6 @@ int ss_update_host(yta_strongsort *e, const double *dets, const int *det_offsets
                                    sizeof(double) * 8 * no[s], hipMemcpyDeviceToHost, e->stream));
     YTA_HIP(host_wait(e->stream));
     e->ntrk = nt;
-    return YTA_OK;
-}
-
-int ss_slot_new(yta_strongsort *e, SsTensorSlot **out) {
-    auto *p = new (std::nothrow) SsTensorSlot();
-    YTA_CHECK(p, YTA_ERR_NOMEM, "out of host memory");
-    e->ring.push_back(p);   // owned from here on (the engine's destructor)
-    const size_t S = e->a.S;
-    YTA_HIP(hipEventCreateWithFlags(&p->in, hipEventDisableTiming));
-    YTA_HIP(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
-    // S ID counters first (8-B aligned), then counts, offsets, track counts
-    YTA_HIP(hipHostMalloc(&p->h, sizeof(long long) * S + sizeof(int) * (3 * S + 1),
-                          hipHostMallocMapped | hipHostMallocCoherent));
-    void *m = nullptr;
-    YTA_HIP(hipHostGetDevicePointer(&m, p->h, 0));
-    auto carve = [S](void *base, long long **nid, int **counts, int **offs, int **live) {
-        *nid = (long long *)base;
-        *counts = (int *)(*nid + S);
-        *offs = *counts + S;
-        *live = *offs + S + 1;
-    };
-    carve(p->h, &p->h_nid, &p->h_counts, &p->h_offs, &p->h_live);
-    carve(m, &p->m_nid, &p->m_counts, &p->m_offs, &p->m_live);
-    *out = p;
-    return YTA_OK;
-}
-
-bool ss_slot_done(SsTensorSlot *p) {
-    if (p->seq < 0) return true;   // never used
-    if (hipEventQuery(p->done) == hipSuccess) return true;
-    (void)hipGetLastError();   // hipErrorNotReady
-    return false;
-}
-
-// A slot no queued frame reads: one whose frame has run (not the newest: n_tracks() reads its
-// counts), else a new one; with SS_RING_MAX frames in flight the call waits for the oldest.
-int ss_slot_acquire(yta_strongsort *e, SsTensorSlot **out) {
-    SsTensorSlot *oldest = nullptr;
-    for (SsTensorSlot *p : e->ring) {
-        if (!p->m_live || p == e->newest) continue;   // m_live null: its allocation failed part way
-        if (ss_slot_done(p)) {
-            *out = p;
-            return YTA_OK;
-        }
-        if (!oldest || p->seq < oldest->seq) oldest = p;
-    }
-    if (e->ring.size() < SS_RING_MAX || !oldest) return ss_slot_new(e, out);
-    ++e->stat[STS_HOST_WAITS];
-    YTA_HIP(hipEventSynchronize(oldest->done));
-    *out = oldest;
     return YTA_OK;
 }
 
@@ -876,6 +874,8 @@ int yta_strongsort_create(int device, int n_streams, int track_capacity, int max
     SS_GET(e->d_off, S + 1);
 #undef SS_GET
     e->ntrk.assign(S, 0);
+    e->ring.slot_bytes = ss_slot_bytes(S);
+    e->ring.host_waits = &e->stat[STS_HOST_WAITS];
     a.nout = e->d_nout;
     a.ntrk_out = e->d_ntrk;
     hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
@@ -1004,61 +1004,42 @@ int yta_strongsort_update_tensors(yta_strongsort *e, void *caller_stream, const 
                                   const double *d_warps, const int *d_active,
                                   const long long *next_id, double *d_rows,
                                   long long rows_capacity, int *d_row_offsets, int *d_row_stream) {
-    YTA_CHECK(e && det_counts && d_row_offsets, YTA_ERR_INVALID, "null argument");
-    YTA_CHECK(dtype == YTA_F64 || dtype == YTA_F32 || dtype == YTA_F16, YTA_ERR_INVALID,
-              "dtype %d is none of YTA_F64, YTA_F32, YTA_F16", dtype);
-    YTA_CHECK(row_stride >= 6, YTA_ERR_INVALID, "row_stride %lld < 6", row_stride);
+    long long total = 0;
+    int rc = tensor_check_args(e, e ? e->a.S : 0, e ? e->a.D : 0, d_dets, dtype, row_stride,
+                               det_counts, d_feats, feat_stride, d_rows, rows_capacity,
+                               d_row_offsets, &total);
+    if (rc) return rc;
     const SsArgs &a = e->a;
     const int S = a.S;
-    long long total = 0;
-    for (int s = 0; s < S; ++s) {
-        YTA_CHECK(det_counts[s] >= 0, YTA_ERR_INVALID, "det_counts[%d] is negative", s);
+    for (int s = 0; s < S; ++s)
         YTA_CHECK(det_counts[s] <= a.MAXD, YTA_ERR_CAPACITY,
                   "stream %d: %d detections > max_dets = %d", s, det_counts[s], a.MAXD);
-        total += det_counts[s];
-    }
-    YTA_CHECK(total <= 0x7fffffffLL, YTA_ERR_INVALID, "%lld detections in one frame", total);
-    const size_t esz = dtype == YTA_F64 ? 8 : dtype == YTA_F32 ? 4 : 2;
-    YTA_CHECK(total == 0 || (d_dets && (uintptr_t)d_dets % esz == 0), YTA_ERR_INVALID,
-              "d_dets null or not aligned to its element size");
-    // every output row is a track matched to one of this frame's detections
-    YTA_CHECK(rows_capacity >= total, YTA_ERR_CAPACITY,
-              "d_rows holds %lld rows, the call needs sum(det_counts) = %lld", rows_capacity, total);
-    YTA_CHECK(total == 0 || (d_rows && (uintptr_t)d_rows % 16 == 0), YTA_ERR_INVALID,
-              "d_rows null or not 16-byte aligned");
-    YTA_CHECK(total == 0 ||
-                  (d_feats && (uintptr_t)d_feats % sizeof(float) == 0 && feat_stride >= a.D),
-              YTA_ERR_INVALID, "d_feats null, misaligned or feat_stride < feat_dim");
     YTA_CHECK(!d_warps || (uintptr_t)d_warps % sizeof(double) == 0, YTA_ERR_INVALID,
               "d_warps misaligned");
-    int rc = select_device(e->device);
+    rc = select_device(e->device);
     if (rc) return rc;
     const hipStream_t cs = (hipStream_t)caller_stream;
-    {   // the cross-stream waits must not end up in somebody's graph
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(cs, &st) != hipSuccess) (void)hipGetLastError();
-        YTA_CHECK(st == hipStreamCaptureStatusNone, YTA_ERR_INVALID, "caller_stream is capturing");
-    }
-    SsTensorSlot *p = nullptr;
-    rc = ss_slot_acquire(e, &p);
+    rc = frame_refuse_capture(cs);
     if (rc) return rc;
-    memcpy(p->h_counts, det_counts, sizeof(int) * S);
-    p->h_offs[0] = 0;
-    for (int s = 0; s < S; ++s) p->h_offs[s + 1] = p->h_offs[s] + det_counts[s];
-    if (next_id) memcpy(p->h_nid, next_id, sizeof(long long) * S);
-    p->seq = ++e->seq;
+    FrameSlot *p = nullptr;
+    rc = e->ring.acquire(&p, e->newest);   // not the newest: n_tracks() reads its counts
+    if (rc) return rc;
+    const SsSlotView hv = ss_slot_view(p->h, S), mv = ss_slot_view(p->m, S);
+    memcpy(hv.counts, det_counts, sizeof(int) * S);
+    hv.offs[0] = 0;
+    for (int s = 0; s < S; ++s) hv.offs[s + 1] = hv.offs[s] + det_counts[s];
+    if (next_id) memcpy(hv.nid, next_id, sizeof(long long) * S);
     e->newest = p;
     ++e->stat[STS_FRAMES];
-    // the engine stream after everything queued on the caller's so far
-    YTA_HIP(hipEventRecord(p->in, cs));
-    YTA_HIP(hipStreamWaitEvent(e->stream, p->in, 0));
+    rc = frame_hand_in(p, cs, e->stream);
+    if (rc) return rc;
     {
         const int cps = (3 * a.MAXD + SS_ING_T - 1) / SS_ING_T;
         const unsigned grid = 1u + (total ? (unsigned)S * cps : 0u);
-        const long long *nid = next_id ? p->m_nid : nullptr;
+        const long long *nid = next_id ? mv.nid : nullptr;
 #define SS_INGEST(T)                                                                             \
     hipLaunchKernelGGL(k_ss_ingest<T>, dim3(grid), dim3(SS_ING_T), 0, e->stream,                 \
-                       (const T *)d_dets, row_stride, p->m_counts, p->m_offs, nid, d_active, S,  \
+                       (const T *)d_dets, row_stride, mv.counts, mv.offs, nid, d_active, S,      \
                        a.MAXD, cps, e->d_ndet, e->d_off, a.hdr, (int)H_N, (int)H_NEXT, e->d_dets)
         if (dtype == YTA_F64) SS_INGEST(double);
         else if (dtype == YTA_F32) SS_INGEST(float);
@@ -1071,17 +1052,13 @@ int yta_strongsort_update_tensors(yta_strongsort *e, void *caller_stream, const 
                    e->d_off, feat_stride);
     e->mask.req_dev = nullptr;
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ss_out_offsets, dim3(1), dim3(SS_OFFS_T), 0, e->stream, e->d_nout, S,
-                       a.CAP, d_row_offsets);
-    hipLaunchKernelGGL(k_ss_pack_rows, dim3(S), dim3(256), 0, e->stream, e->d_out,
-                       (long long)a.CAP, e->d_ntrk, S, d_row_offsets, d_rows, rows_capacity,
-                       d_row_stream, p->m_live);
+    hipLaunchKernelGGL(k_tp_out_offsets<SsNOut>, dim3(1), dim3(TP_OFFS_T), 0, e->stream,
+                       SsNOut{e->d_nout}, S, a.CAP, d_row_offsets, (int *)nullptr);
+    hipLaunchKernelGGL(k_tp_pack_rows<SsLive>, dim3(S), dim3(256), 0, e->stream, e->d_out,
+                       (long long)a.CAP, S, d_row_offsets, d_rows, rows_capacity, d_row_stream,
+                       SsLive{e->d_ntrk, mv.live});
     YTA_HIP(hipGetLastError());
-    // the caller's stream after the frame's last launch: its later work sees the outputs and may
-    // free or overwrite the inputs
-    YTA_HIP(hipEventRecord(p->done, e->stream));
-    YTA_HIP(hipStreamWaitEvent(cs, p->done, 0));
-    return YTA_OK;
+    return frame_hand_back(p, cs, e->stream);
 }
 
 int yta_strongsort_tensor_stats(yta_strongsort *e, long long *out, int n) {

@@ -155,8 +155,8 @@ class TensorFrame:
 
 
 class TensorPath:
-    """update_tensors' companions for the OC-SORT family's and StrongSORT's engines (`_abi` names
-    the C prefix: yta_<_abi>_tensor_stats / _next_ids / _sync)."""
+    """update_tensors' companions for the trackers' engines (`_abi` names the C prefix:
+    yta_<_abi>_tensor_stats / _next_ids / _sync)."""
     _abi = None
 
     def _call(self, name, *args):

@@ -11,13 +11,14 @@ import numpy as np
 
 from .. import _lib
 from ._streams import StreamSubset
-from ._tensors import is_cuda_tensor
+from ._tensors import TensorPath, is_cuda_tensor
 from .basetrack import BaseTrack, TrackState
 
 
-class ByteTrackEngine(StreamSubset):
+class ByteTrackEngine(StreamSubset, TensorPath):
     """S independent ByteTrack streams sharing one device engine (one launch per kernel covers
     every stream).  Stream s has its own tracks and ID counter."""
+    _abi = "bytetrack"   # BoTSORTEngine inherits it: the yta_bytetrack_* companions serve both
 
     def __init__(self, n_streams=1, track_thresh=0.45, match_thresh=0.8, track_buffer=25,
                  frame_rate=30, device=0, track_capacity=256, max_dets=128):
@@ -186,25 +187,6 @@ class ByteTrackEngine(StreamSubset):
         _lib.check(self.lib.yta_bytetrack_update_tensors(self._h, *f.common_head(),
                                                          *f.common_tail()))
         return f.result()
-
-    def tensor_stats(self):
-        """Accounting of update_tensors (yta_bytetrack_tensor_stats): frames enqueued, calls that
-        blocked on the device, engine growths, float64 frames read in place."""
-        names = ["frames", "host_waits", "reserves", "ingest_skipped"]
-        buf = (ctypes.c_longlong * len(names))()
-        _lib.check(self.lib.yta_bytetrack_tensor_stats(self._h, buf, len(names)))
-        return {k: int(buf[i]) for i, k in enumerate(names)}
-
-    def next_ids(self):
-        """The S per-stream ID counters on the device (waits for the engine's stream)."""
-        nid = np.zeros(self.n_streams, dtype=np.int64)
-        _lib.check(self.lib.yta_bytetrack_next_ids(self._h, _lib.ptr(nid)))
-        return nid
-
-    def sync(self):
-        """Wait for the engine's stream; raises if a frame since the last wait set a device
-        error flag."""
-        _lib.check(self.lib.yta_bytetrack_sync(self._h))
 
     def state(self, stream=0):
         """Live tracks of one stream (tracked list then lost list) for parity checks."""
