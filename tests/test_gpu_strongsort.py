@@ -1,11 +1,15 @@
 """GPU: StrongSORT on the device (csrc/strongsort.hip, csrc/lsa_replay.hpp through the C ABI)
 against its restatement (tests/strongsort_oracle.py), bit for bit, and against the reference's
-goldens (tests/golden/strongsort_synth.npz: ids / conf / cls / det_ind exact, boxes 1e-9)."""
+goldens (tests/golden/strongsort_synth.npz: ids / conf / cls / det_ind exact, boxes 1e-9); above
+one block, one tile and one loop trip on the inputs of tests/strongsort_big.py, with SciPy itself
+as the solver's reference."""
 import os
 
 import numpy as np
 import pytest
+from scipy.optimize import linear_sum_assignment
 
+import strongsort_big as big
 import strongsort_oracle as so
 from conftest import GOLDEN
 from yolo_tracking_amd import _lib
@@ -67,7 +71,80 @@ def test_lsa_replay_against_restatement(shape):
         assert np.array_equal(r, er) and np.array_equal(q, eq), shape
 
 
+# ---------------------------------------------------------------- solver above one block (512)
+# Every thread of lsa_replay_block takes several trips of the relax / select, init and dual-update
+# loops and merges candidates into its own (value, rank) key before the butterfly; from 1365 rows
+# or columns on the work arrays need the opt-in dynamic LDS.
+BIG_SHAPES = [(513, 513), (600, 700), (700, 600), (1100, 900), (1000, 1600), (3072, 3072)]
+KQ = [(3, 0), (3, 8), (12, 4)]
+
+
+def _solver_case(c, decisive=True):
+    """The device against SciPy itself and, up to 1100 x 900, against the restatement.  With
+    `decisive` the expected answer must have been placed by the tie-breaking rule
+    (strongsort_big.is_decisive)."""
+    refs = [linear_sum_assignment(c)]
+    if max(c.shape) <= 1100:
+        refs.append(so.lsa_replay(c))
+    r, q = _lib.lsa_replay(c)
+    for er, eq in refs:
+        if decisive:
+            assert big.is_decisive(c, er, eq), c.shape
+        assert np.array_equal(r, er), c.shape
+        assert np.array_equal(q, eq), (c.shape, int((q != eq).sum()))
+
+
+@pytest.mark.parametrize("shape,kq", [(s, kq) for s in BIG_SHAPES for kq in KQ
+                                      if s[0] < 3072 or kq[0] == 3],    # 3072: k = 3 only
+                         ids=lambda v: f"{v[0]}x{v[1]}")
+def test_lsa_replay_sparse_clamped(shape, kq):
+    k, quant = kq
+    _solver_case(big.sparse_clamped(*shape, seed=100 * k + quant, k=k, quant=quant))
+
+
+@pytest.mark.parametrize("shape", [(700, 600), (600, 700)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_lsa_replay_structured(shape):
+    _solver_case(big.last_columns(*shape, seed=7))
+    _solver_case(big.first_rows_hopeless(*shape, seed=8))
+    # all equal: nothing but the tie rule produces the answer, yet SciPy's is the identity, whose
+    # columns ascend, so the decisiveness check does not apply to this one case
+    _solver_case(np.full(shape, big.TOP), decisive=False)
+
+
+@pytest.mark.parametrize("shape", [(3073, 4), (4, 3073)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_lsa_replay_refuses_more_than_3072(shape):
+    with pytest.raises(_lib.YTAError) as e:
+        _lib.lsa_replay(np.zeros(shape))
+    assert e.value.code == _lib.YTA_ERR_INVALID and "3072" in str(e.value)
+
+
+def test_lsa_replay_infeasible_then_valid():
+    c = big.sparse_clamped(600, 700, seed=5, k=3)
+    bad = c.copy()
+    bad[301] = np.inf
+    with pytest.raises(_lib.YTAError) as e:
+        _lib.lsa_replay(bad)
+    assert e.value.code == _lib.YTA_ERR_INVALID and "infeasible" in str(e.value)
+    r, q = _lib.lsa_replay(c)                     # the next call is not affected
+    er, eq = so.lsa_replay(c)
+    assert np.array_equal(r, er) and np.array_equal(q, eq)
+
+
 # -------------------------------------------------------------------- gallery distance, Kalman
+@pytest.mark.parametrize("shape", big.GALLERY_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_nn_cosine_min_across_tiles(shape):
+    """More than one block of detections (128), all four waves of a block, gallery lengths on,
+    one below and one above the 32-row tile, D off the 16-wide k step; the rows past a track's
+    length would win the minimum with cost 0 if they were read."""
+    gal, lens, feats, poisoned = big.gallery_case(*shape)
+    exp = so.nn_cosine_min(gal, lens, feats)
+    assert poisoned and min(exp[t, j] for t, j in poisoned) > 0.1
+    got = _lib.nn_cosine_min(gal, lens, feats)
+    assert got.dtype == np.float32 and got.shape == exp.shape
+    bad = np.argwhere(got != exp)
+    assert len(bad) == 0, (shape, len(bad), bad[:5].tolist())
+
+
 @pytest.mark.parametrize("D", [1, 96, 512])
 @pytest.mark.parametrize("B", [1, 7, 100])
 def test_nn_cosine_min_bit_exact(B, D):
@@ -125,9 +202,9 @@ def test_kf_gating_kat():
 
 
 # --------------------------------------------------------------------------------------- engine
-def _engine(n_streams, p, D=32):
+def _engine(n_streams, p, D=32, cap=96, maxd=48):
     from yolo_tracking_amd import StrongSortEngine
-    return StrongSortEngine(n_streams, feat_dim=D, device=0, track_capacity=96, max_dets=48, **p)
+    return StrongSortEngine(n_streams, feat_dim=D, device=0, track_capacity=cap, max_dets=maxd, **p)
 
 
 def _check_state(eng, stream, orc):
@@ -200,6 +277,72 @@ def test_engine_three_streams_in_one_engine(runs):
             else:
                 assert len(got[s]) == 0, (names[s], f)   # no detection, no output row
     assert eng.n_tracks().tolist() == [len(eng.state(s)["id"]) for s in range(3)]
+
+
+# ------------------------------------------------------------------------------ engine at size
+@pytest.fixture(scope="module")
+def bigrun():
+    """The restatement over strongsort_big's stream (shared with the tensor-path tests); its
+    property assertions (both stage-1 orientations and a stage 2 above 512, more than 256 births,
+    deletions beside births, hopeless rows) run inside."""
+    return big.big_run()
+
+
+def _big_engine(n_streams):
+    return _engine(n_streams, big.BIG_P, D=big.BIG_D, cap=big.BIG_CAP, maxd=big.BIG_CAP)
+
+
+def test_engine_big_stream_bit_exact(bigrun):
+    eng = _big_engine(1)
+    for again, frames in enumerate((bigrun.frames, bigrun.frames[:3])):
+        for f, (d, ft, w) in enumerate(frames):
+            got = eng.update([d], [ft], [w] if eng.n_tracks()[0] >= 1 else None)[0]
+            exp = bigrun.rows[f]
+            assert got.shape == exp.shape, (again, f, got.shape, exp.shape)
+            assert np.array_equal(got, exp), (again, f, np.argwhere(got != exp)[:4].tolist())
+            assert eng.n_tracks()[0] == bigrun.ntrk[f], (again, f)
+        if not again:
+            _check_state(eng, 0, bigrun.oracle)
+            eng.reset()
+            assert eng.n_tracks()[0] == 0 and len(eng.state(0)["id"]) == 0
+
+
+def test_engine_big_stream_two_streams(bigrun):
+    """S = 2: stream 1 is the same stream two frames late (empty frames first), so at every
+    launch the two streams are at different sizes; ids restart per stream.  A wrong s * CAP *
+    MAXD stride lands inside the other stream's data at this size, and with max_dets below
+    track_capacity so does one stride taken for the other."""
+    fr, nf, lag = bigrun.frames, len(bigrun.frames), 2
+    empty = (np.zeros((0, 6)), np.zeros((0, big.BIG_D), np.float32), None)
+    maxd = 768
+    assert 512 < max(len(d) for d, _, _ in fr) <= maxd < big.BIG_CAP
+    eng = _engine(2, big.BIG_P, D=big.BIG_D, cap=big.BIG_CAP, maxd=maxd)
+    for f in range(nf + lag):
+        at = (f, f - lag)
+        ins = [fr[g] if 0 <= g < nf else empty for g in at]
+        nt = eng.n_tracks()
+        got = eng.update([d for d, _, _ in ins], [ft for _, ft, _ in ins],
+                         [w if w is not None and nt[s] >= 1 else None
+                          for s, (_, _, w) in enumerate(ins)])
+        for s, g in enumerate(at):
+            if 0 <= g < nf:
+                assert np.array_equal(got[s], bigrun.rows[g]), (s, g)
+                assert eng.n_tracks()[s] == bigrun.ntrk[g], (s, g)
+            else:
+                assert len(got[s]) == 0, (s, g)              # no detection, no output row
+        if f == nf - 1:
+            _check_state(eng, 0, bigrun.oracle)
+    _check_state(eng, 1, bigrun.oracle)
+
+
+def test_engine_at_the_solver_limit(runs):
+    """track_capacity = max_dets = 3072: k_ss_match runs with the solver's largest work arrays
+    (about 147 KB of opt-in dynamic LDS); the answers are stream a's."""
+    p, frames, rows, exp, orc = runs["a"]
+    eng = _engine(1, p, cap=3072, maxd=3072)
+    assert eng.capacity() == (3072, 3072)
+    _run_single(eng, frames, exp, rows)
+    _check_state(eng, 0, orc)
 
 
 class _FakeReID:

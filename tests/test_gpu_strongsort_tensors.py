@@ -1,5 +1,6 @@
 """GPU: StrongSORT's tensor path (yta_strongsort_update_tensors), stream subsets and per-stream
-reset.  Inputs are the golden streams of tests/golden/strongsort_synth.npz; the expected values
+reset.  Inputs are the golden streams of tests/golden/strongsort_synth.npz and, for frames of
+several hundred detections, the stream of tests/strongsort_big.py; the expected values
 come from the host-buffer update() of a second engine on the same (cast) values, from the goldens
 and from the restatement (tests/strongsort_oracle.py), never from the tensor path itself."""
 import ctypes
@@ -8,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import strongsort_big as big
 import strongsort_oracle as so
 from conftest import GOLDEN
 from yolo_tracking_amd import _lib
@@ -190,6 +192,45 @@ def test_awkward_layouts(ref, layout, dt):
     for s in range(3):
         assert _same_state(eng.state(s), states[s]), s
     assert eng.tensor_stats()["frames"] == len(seq)
+
+
+# ---------------------------------------------------------------------------- 2b. a big frame
+@pytest.fixture(scope="module")
+def bigrun():
+    """strongsort_big's stream and the restatement's run over it (computed once per process and
+    shared with test_gpu_strongsort.py)."""
+    return big.big_run()
+
+
+def _wide_and_padded(fr, dt):
+    """dets a column slice of a 9-wide tensor, feats packed rows three floats wider than D."""
+    a = _packed(fr, dt)
+    n, fd = a["feats"].shape
+    wide = torch.full((n, 9), float("nan"), dtype=TORCH_DT[dt], device=DEV)
+    wide[:, 2:8] = a["dets"]
+    fw = torch.full((n, fd + 3), float("nan"), dtype=torch.float32, device=DEV)
+    fw[:, 1:fd + 1] = a["feats"]
+    return dict(a, dets=wide[:, 2:8], feats=fw[:, 1:fd + 1])
+
+
+@pytest.mark.parametrize("layout,dt", [(_plain, "f32"), (_plain, "f16"), (_wide_and_padded, "f32")],
+                         ids=lambda v: v if isinstance(v, str) else v.__name__)
+def test_big_stream_against_update(bigrun, layout, dt):
+    """strongsort_big's stream (several hundred detections a frame: with max_dets = 1024
+    k_ss_ingest runs 12 chunk blocks a stream) through update_tensors against update() of a second
+    engine on the same cast values; update() itself is pinned to the restatement on this stream by
+    test_gpu_strongsort.py::test_engine_big_stream_bit_exact."""
+    run = bigrun
+    kw = dict(feat_dim=big.BIG_D, track_capacity=big.BIG_CAP, max_dets=big.BIG_CAP)
+    seq = [[(d.astype(NP_DT[dt]).astype(np.float64), ft, w)] for d, ft, w in run.frames]
+    assert all(np.isfinite(fr[0][0]).all() for fr in seq) and max(len(fr[0][0]) for fr in seq) > 512
+    rows, gates, host = _host_run(run.p, seq, _engine(1, run.p, **kw))
+    assert sum(len(r[0]) for r in rows) > 2000
+    eng = _engine(1, run.p, **kw)
+    _tensor_run(eng, seq, rows, gates, dt, layout=layout)
+    assert np.array_equal(eng.n_tracks(), host.n_tracks()) and host.n_tracks()[0] > 512
+    assert _same_state(eng.state(0), host.state(0))
+    eng.sync()                                   # no capacity or solver error was left behind
 
 
 def test_one_stream_and_a_frame_without_any_detection(golden):

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import strongsort_big as big
 import strongsort_oracle as so
 from conftest import GOLDEN
 
@@ -37,14 +38,41 @@ def clamped_cases(nr, nc, seed):
     return out
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+# above the device solver's block size (512), where the GPU tests lean on the restatement
+BIG_SHAPES = [(513, 513), (700, 600), (600, 700)]
+
+
+@pytest.mark.parametrize("shape", SHAPES + BIG_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_lsa_replay_equals_scipy(shape):
     scipy_optimize = pytest.importorskip("scipy.optimize")
+    if shape in BIG_SHAPES:
+        for k, quant in ((3, 0), (3, 8), (12, 4)):
+            c = big.sparse_clamped(*shape, seed=100 * k + quant, k=k, quant=quant)
+            r, q = scipy_optimize.linear_sum_assignment(c)
+            assert big.is_decisive(c, r, q), (shape, k, quant)   # the ties place the pairs
+            r2, q2 = so.lsa_replay(c)
+            assert np.array_equal(r, r2) and np.array_equal(q, q2), (shape, k, quant)
+        return
     for seed in range(6):
         for c in clamped_cases(*shape, seed):
             r, k = scipy_optimize.linear_sum_assignment(c)
             r2, k2 = so.lsa_replay(c)
             assert np.array_equal(r, r2) and np.array_equal(k, k2), (shape, seed, c)
+
+
+@pytest.mark.parametrize("shape", big.GALLERY_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_nn_cosine_min_against_float64(shape):
+    """The restatement's pinned float32 order against min(1 - g.f) over float64-normalised rows,
+    at the shapes of the GPU test that is bit-exact against the restatement.  Bound (D + 16) *
+    2^-24: unit vectors, so each of the D fma steps rounds a partial sum of magnitude <= 1 (half
+    an ulp of 1 = 2^-24 at most), plus a few roundings for the two normalisations and 1 - dot."""
+    T, B, D, M = shape
+    gal, lens, feats, _ = big.gallery_case(*shape)
+    got = so.nn_cosine_min(gal, lens, feats)
+    err = float(np.abs(got.astype(np.float64) - big.nn_cosine_min_f64(gal, lens, feats)).max())
+    print(f"nn_cosine_min {shape}: max |float32 order - float64| = {err:.3g}, "
+          f"bound {(D + 16) * 2.0 ** -24:.3g}")
+    assert err <= (D + 16) * 2.0 ** -24
 
 
 @pytest.fixture(scope="module")
