@@ -1036,7 +1036,8 @@ int yta_osnet_gate_sum(const void *stack, const void *gate, int N, int C, int P,
  *                                 + sum_{k < k2} w[g][k1 + k][co] x2[n][k][p]
  *                                 + bias[g cout_g + co] + res[n][g cout_g + co][p] )
  * w: float32 [G][k1 + k2][cout_g] (k-major: BatchNorm folded, transposed); bias, x2 (k2 = 0),
- * res may be NULL.  relu: 0 none, 1 ReLU, 2 ReLU6 (clamp to [0, 6]: mobilenetv2.py ConvBlock). */
+ * res may be NULL.  relu: 0 none, 1 ReLU, 2 ReLU6 (clamp to [0, 6]: mobilenetv2.py ConvBlock),
+ * 3 ReLU on both sides of the residual, relu(relu(. + bias) + res) (mlfn.py:87-92). */
 typedef struct yta_pw_args {
     const void *x1;
     long long x1n, x1c, x1p;
@@ -1113,6 +1114,46 @@ int yta_mbv2_dw3x3(const void *x, const float *w, const float *b, int N, int C, 
 int yta_mbv2_expand_dw(const void *x, const float *w1, const float *b1, const float *wdw,
                        const float *b2, int N, int Cin, int Cmid, int H, int W, int stride,
                        int half, void *y, void *stream);
+
+/* ---- MLFN (boxmot/appearance/backbones/mlfn.py; appearance/mlfn.py).  The conventions of the
+ * OSNet and MobileNetV2 kernels: device pointers, asynchronous on `stream`, NCHW planes, float32
+ * (half = 0) or float16 (half = 1) storage, float32 arithmetic, BatchNorms folded into float32
+ * weights and biases, no atomics (the same input gives the same bits).  The stem (:182-184, the
+ * bias of conv1 folded into the BatchNorm's) is yta_osnet_stem, the max pool (:185) and the plane
+ * means (:42, :193) yta_osnet_pool kinds 0 and 2; fm_conv1 (:66-68), fm_conv3 with both ReLUs
+ * and the residual (:85-92, relu = 3; where the block has a downsample, fm_conv3 runs with
+ * relu = 1 and is the res of the downsample's 1x1, relu = 1), fc_x and fc_s (:194-195) are
+ * yta_osnet_pointwise.
+ * yta_mlfn_gconv3x3: MLFNBlock.fm_conv2, fm_bn2, ReLU and the factor selection (:71-82) in one
+ * launch: a grouped 3x3 convolution, zero padding 1, stride 1 or 2, G groups of n = C / G
+ * channels (w float32 C x n x 9, b float32 C), then
+ *   y[b][c] = relu(conv(x)[b][c] + b[c]) * scale[b * scale_stride + c / n],
+ * x N x C x H x W -> y N x C x ((H-1)/stride+1) x ((W-1)/stride+1).  Channel c takes the scale of
+ * group c / n: the reference's repeat / view / permute (:78-81) gives s[g] to channels g n ..
+ * g n + n - 1, not to c % G.  scale float32, N rows of G with a row stride in elements (a slot of
+ * the N x 16 G selection buffer); NULL: a plain grouped convolution + bias + ReLU.  C, G (dividing
+ * C), H and W are arbitrary; N and G at most 65535.
+ * yta_mlfn_fsm: MLFNBlock.fsm (:41-52) after its average pool: pooled N x cin plane means in the
+ * storage type (yta_osnet_pool kind 2 of the block input), three 1x1 layers with bias (w1
+ * [cin][f0], w2 [f0][f1], w3 [f1][G]: float32, k-major as yta_osnet_pointwise takes them), ReLU,
+ * ReLU, sigmoid.  The result, rounded to the storage type, goes to sel[n * sel_stride + g]
+ * (float32: the scale of yta_mlfn_gconv3x3 and, with float32 storage, the input of fc_s) and, when
+ * sel_t is not NULL, to sel_t[n * sel_t_stride + g] in the storage type (fc_s's input with
+ * float16 storage).  cin + f0 + f1 <= 3072.
+ * yta_mlfn_subsample: y = x[:, :, ::stride, ::stride], the pixels the stride-2 1x1 downsample
+ * (:57, :90) reads: x N x C x H x W -> y N x C x ((H-1)/stride+1) x ((W-1)/stride+1).
+ * yta_mlfn_mean2: y = (a + b) * 0.5 over count elements (:197). */
+int yta_mlfn_gconv3x3(const void *x, const float *w, const float *b, const float *scale,
+                      long long scale_stride, int N, int C, int G, int H, int W, int stride,
+                      int half, void *y, void *stream);
+int yta_mlfn_fsm(const void *pooled, int N, int cin, int f0, int f1, int G, const float *w1,
+                 const float *b1, const float *w2, const float *b2, const float *w3,
+                 const float *b3, int half, float *sel, long long sel_stride, void *sel_t,
+                 long long sel_t_stride, void *stream);
+int yta_mlfn_subsample(const void *x, int N, int C, int H, int W, int stride, int half, void *y,
+                       void *stream);
+int yta_mlfn_mean2(const void *a, const void *b, long long count, int half, void *y,
+                   void *stream);
 
 #ifdef __cplusplus
 }

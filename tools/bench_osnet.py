@@ -7,7 +7,9 @@ network alone and for the whole get_features path, float32 and float16.  Prints 
 --variant mobilenetv2_x1_0 / mobilenetv2_x1_4 (appearance/mobilenetv2.py) runs the same measurement
 on MobileNetV2: the HIP forward with the fused expand + depthwise kernel ("fused": true), with the
 two layers as two launches ("fused": false), and the same folded graph on PyTorch's kernels in
-NHWC and NCHW ("hip_blocks": false), the baseline a model=<torch module> user gets."""
+NHWC and NCHW ("hip_blocks": false), the baseline a model=<torch module> user gets.
+--variant mlfn (appearance/mlfn.py) measures the MLFN HIP forward against the same folded graph on
+PyTorch's kernels (hip=False, "hip_blocks": false) on the same device, float32 and float16."""
 import argparse
 import json
 import os
@@ -22,16 +24,19 @@ sys.path.insert(0, REPO)
 
 def main():
     ap = argparse.ArgumentParser()
+    from yolo_tracking_amd.appearance.mlfn import VARIANTS as MLFN
     from yolo_tracking_amd.appearance.mobilenetv2 import VARIANTS as MBV2
     from yolo_tracking_amd.appearance.osnet import VARIANTS
-    ap.add_argument("--variant", default="osnet_x0_25", choices=sorted(VARIANTS) + sorted(MBV2),
+    ap.add_argument("--variant", default="osnet_x0_25",
+                    choices=sorted(VARIANTS) + sorted(MBV2) + sorted(MLFN),
                     help="OSNet variant (plain, osnet_ibn_* or osnet_ain_*; default osnet_x0_25) "
-                         "or mobilenetv2_x1_0 / mobilenetv2_x1_4")
+                         "or mobilenetv2_x1_0 / mobilenetv2_x1_4, or mlfn")
     ap.add_argument("--crops", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=10)
     args = ap.parse_args()
     import torch
     from yolo_tracking_amd.appearance import ReIDDetectMultiBackend
+    from yolo_tracking_amd.appearance.mlfn import MLFNReID
     from yolo_tracking_amd.appearance.mobilenetv2 import MobileNetV2ReID
     from yolo_tracking_amd.appearance.osnet import OSNetReID
     rng = np.random.default_rng(0)
@@ -40,8 +45,10 @@ def main():
     wh = rng.uniform(48, 192, (n, 2))
     xy = rng.uniform(0, 1, (n, 2)) * [W - 200, H - 200]
     boxes = np.concatenate([xy, xy + wh], 1)
-    mbv2 = args.variant in MBV2
-    if mbv2:   # (half, chunk, hip, channels_last, fused)
+    mbv2, mlfn = args.variant in MBV2, args.variant in MLFN
+    if mlfn:   # the HIP forward and the folded graph on PyTorch's kernels, NCHW
+        configs = [(half, 1024, hip, False, None) for half in (False, True) for hip in (True, False)]
+    elif mbv2:   # (half, chunk, hip, channels_last, fused)
         configs = [(half, 1024, hip, cl, fused) for half in (False, True)
                    for hip, cl, fused in ((True, False, True), (True, False, False),
                                           (False, True, None), (False, False, None))]
@@ -51,7 +58,9 @@ def main():
             (True, 256, True, False), (False, 1024, False, True), (True, 1024, False, True),
             (True, 1024, False, False))]
     for half, chunk, hip, cl, fused in configs:
-        if mbv2:
+        if mlfn:
+            net = MLFNReID(args.variant, None, device="cuda:0", half=half, chunk=chunk, hip=hip)
+        elif mbv2:
             net = MobileNetV2ReID(args.variant, None, device="cuda:0", half=half, chunk=chunk,
                                   channels_last=cl, hip=hip, fused=bool(fused))
         else:
@@ -77,7 +86,8 @@ def main():
         for _ in range(args.steps):
             reid.get_features(boxes, img)
         e2e_ms = 1000 * (time.perf_counter() - t0) / args.steps
-        print(json.dumps({"metric": ("MobileNetV2" if mbv2 else "OSNet") + " ReID crops/s",
+        print(json.dumps({"metric": ("MLFN" if mlfn else "MobileNetV2" if mbv2 else "OSNet") +
+                          " ReID crops/s",
                           "variant": args.variant, "fused": fused,
                           "dtype": "f16" if half else "f32", "crops": n, "chunk": chunk,
                           "layout": "nhwc" if cl else "nchw", "hip_blocks": hip,

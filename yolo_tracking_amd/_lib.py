@@ -289,6 +289,12 @@ _SIGS = {
     "yta_mbv2_stem": ([_P, _I, _I, _I, _P, _P, _I, _I, _P, _P], _I),
     "yta_mbv2_dw3x3": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
     "yta_mbv2_expand_dw": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P], _I),
+    "yta_mlfn_gconv3x3": ([_P, _P, _P, _P, ctypes.c_longlong, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+                          _I),
+    "yta_mlfn_fsm": ([_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, ctypes.c_longlong,
+                      _P, ctypes.c_longlong, _P], _I),
+    "yta_mlfn_subsample": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
+    "yta_mlfn_mean2": ([_P, _P, ctypes.c_longlong, _I, _P, _P], _I),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

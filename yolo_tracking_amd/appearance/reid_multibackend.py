@@ -16,8 +16,8 @@ channels-last, batched branches) built from `weights` as the reference builds it
 file name (reid_multibackend.py:57-80): osnet_x0_25 .. osnet_x1_0, and the instance-norm members
 of the family, osnet_ibn_x1_0 and osnet_ain_x1_0 (and their narrower widths), whose norms run in
 csrc/osnet.hip as well, or MobileNetV2 (appearance/mobilenetv2.py: mobilenetv2_x1_0 and
-mobilenetv2_x1_4, csrc/mbv2.hip); the reference's .pt state dicts
-load unchanged (torch.load(weights_only=True)).  A weight file that is not on disk would be
+mobilenetv2_x1_4, csrc/mbv2.hip), or MLFN (appearance/mlfn.py: mlfn, csrc/mlfn.hip); the
+reference's .pt state dicts load unchanged (torch.load(weights_only=True)).  A weight file that is not on disk would be
 downloaded by the reference (gdown, :61-64) or end the program (:67-72); there is no network here,
 so a missing file raises FileNotFoundError.  Freshly initialised weights (benchmarks, plumbing
 tests) are an explicit opt-in: `random_init=True`.  `model=` (any torch module on the device
@@ -106,17 +106,20 @@ class ReIDDetectMultiBackend:
     def _build_osnet(self, weights):
         """reid_multibackend.py:57-80 as a dispatch on the weight file name: the OSNet family
         first (the plain widths, the trackers' default weights, osnet_ibn_* and osnet_ain_*:
-        appearance/osnet.py VARIANTS), then MobileNetV2 (appearance/mobilenetv2.py VARIANTS)."""
-        from . import mobilenetv2, osnet
-        for family, cls in ((osnet, osnet.OSNetReID), (mobilenetv2, mobilenetv2.MobileNetV2ReID)):
+        appearance/osnet.py VARIANTS), then MobileNetV2 (appearance/mobilenetv2.py VARIANTS),
+        then MLFN (appearance/mlfn.py VARIANTS)."""
+        from . import mlfn, mobilenetv2, osnet
+        for family, cls in ((osnet, osnet.OSNetReID), (mobilenetv2, mobilenetv2.MobileNetV2ReID),
+                            (mlfn, mlfn.MLFNReID)):
             name = family.model_name(weights)
             if name is not None:
                 break
         else:
             raise NotImplementedError(
                 f"ReID weights {str(weights)!r}: only the OSNet family (osnet_x0_25 .. osnet_x1_0, "
-                "osnet_ibn_x1_0, osnet_ain_x1_0 and their other widths) and MobileNetV2 "
-                "(mobilenetv2_x1_0, mobilenetv2_x1_4) are rebuilt on the MI355X path; pass "
+                "osnet_ibn_x1_0, osnet_ain_x1_0 and their other widths), MobileNetV2 "
+                "(mobilenetv2_x1_0, mobilenetv2_x1_4) and MLFN (mlfn) are rebuilt on the MI355X "
+                "path; pass "
                 "model=<torch module> for other networks")
         w = Path(weights)
         if w.is_file():

@@ -15,7 +15,8 @@
 //              one wave per 32 (output channels) x 32 (pixels) tile, operands straight from
 //              global memory (the pixel axis is contiguous: B fragments are coalesced rows), groups,
 //              a second input segment (the downsample branch joins conv3's sum), bias, identity
-//              residual and ReLU (relu = 1) or ReLU6 (relu = 2) fused in the epilogue;
+//              residual and ReLU (relu = 1), ReLU6 (relu = 2) or a ReLU on both sides of the
+//              residual (relu = 3: MLFN's block end) fused in the epilogue;
 //   k_stem     conv 7x7 stride 2 pad 3 (3 -> C0) + bias + ReLU, input tile + halo in LDS,
 //              16 output channels per pass in registers, weights broadcast from LDS;
 //   k_pool     max 3x3 stride 2 pad 1 / average 2x2 stride 2 / global mean (OSNet's pools);
@@ -237,6 +238,7 @@ __global__ __launch_bounds__(PW_T) void k_pw(yta_pw_args a) {
             const long long ch = (long long)g * a.cout_g + c;
             float v = acc[m][q];
             if (a.bias) v += a.bias[ch];
+            if (a.relu == 3) v = fmaxf(v, 0.f);   // mlfn.py:87: the ReLU ahead of the residual
             if (res) v += (float)res[ch * a.rc + (long long)p * a.rp];
             if (a.relu) v = fmaxf(v, 0.f);
             if (a.relu == 2) v = fminf(v, 6.f);   // ReLU6 (MobileNetV2's ConvBlock)
