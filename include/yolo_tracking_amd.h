@@ -502,6 +502,22 @@ int yta_ocsort_stats(yta_ocsort *engine, long long *stats);
  * new - round 5 wrote 4 values with no length, round 4 three). */
 int yta_ocsort_lap_stats(yta_ocsort *engine, long long *stats, int n);
 int yta_ocsort_hip_stream(yta_ocsort *engine, void **stream);
+/* Test-only snapshot of the stage-1 matrices, which the later rounds of a frame overwrite.  Off
+ * by default (one host branch per update).  When on, yta_ocsort_update / _update_device /
+ * _update_streams copy the matrices device to device on the engine's stream, after the last cost
+ * kernel and before the first solver kernel; results and launch order are otherwise unchanged.
+ * yta_ocsort_update_tensors refuses (YTA_ERR_INVALID) while the switch is on.  Enabling or
+ * disabling waits for the engine's stream; disabling frees the copies. */
+int yta_ocsort_debug_costs_enable(yta_ocsort *engine, int on);
+/* The last update's snapshot of one stream (waits for the engine's stream).  dims[0] = n_high (the
+ * matrix rows: first-round detections), dims[1] = n_trk (the columns: trackers after prediction
+ * and NaN culling).  rows: n_high input-row indices of the matrix rows; ids: n_trk track ids of
+ * the columns; boxes: n_trk x 4 predicted boxes (x1, y1, x2, y2) of the columns, the association
+ * function's tracker inputs; asso, cost: n_high x n_trk row-major, the association function's
+ * values and -(asso + angle).  Every array may be NULL (then not written): call once for dims, then with
+ * arrays of those sizes. */
+int yta_ocsort_debug_costs(yta_ocsort *engine, int stream, int *dims, int *rows, long long *ids,
+                           double *boxes, double *asso, double *cost);
 /* OCSORT Kalman KAT: n tracks initialised from z0 (n x 4, [u, v, s, r]) run `steps` steps of
  * predict + update(z[step] (n x 4 per step); a NaN first value = update(None)), freeze /
  * unfreeze included; final x (n x 7) and full P (n x 49). */
@@ -593,6 +609,17 @@ int yta_deepocsort_stats(yta_deepocsort *engine, long long *stats);
  * rounds (BYTE / OCR) solved on the rows and columns that have a positive entry. */
 int yta_deepocsort_lap_stats(yta_deepocsort *engine, long long *stats, int n);
 int yta_deepocsort_hip_stream(yta_deepocsort *engine, void **stream);
+/* As yta_ocsort_debug_costs_enable / yta_ocsort_debug_costs.  dims: n_high, n_trk, n_pos (1: the
+ * frame ran the dense embedding tiles and row scans), col_ovf (1: a column listed more pairs than
+ * fit, so the column weights came from the dense scan).  asso, emb, cost: n_high x n_trk; rw:
+ * n_high and cw: n_trk adaptive weights (defined with embeddings on and aw_off = 0).  emb holds the
+ * dot products as stored: defined only where asso is not <= 0 (elsewhere the listed-pair path
+ * writes nothing, and every reader takes 0 there, association.py:165).  cost is the final
+ * -(asso + angle + embedding term). */
+int yta_deepocsort_debug_costs_enable(yta_deepocsort *engine, int on);
+int yta_deepocsort_debug_costs(yta_deepocsort *engine, int stream, int *dims, int *rows,
+                               long long *ids, double *boxes, double *asso, double *emb,
+                               double *rw, double *cw, double *cost);
 /* DeepOCSORT Kalman KAT (deep_ocsort.py:103-136, 198-293 new-KF branch): n tracks initialised
  * from boxes b0 (n x 4, x1 y1 x2 y2) run `steps` steps of [affine (warps: steps x n x 6, NULL =
  * none)], predict + update(b[step] (n x 4); a NaN first value = update(None)) with the reference's
@@ -677,6 +704,11 @@ int yta_hybridsort_stats(yta_hybridsort *engine, long long *stats);
  * rounds (BYTE / OCR) solved on the rows and columns that have a positive entry. */
 int yta_hybridsort_lap_stats(yta_hybridsort *engine, long long *stats, int n);
 int yta_hybridsort_hip_stream(yta_hybridsort *engine, void **stream);
+/* As yta_ocsort_debug_costs_enable / yta_ocsort_debug_costs.  emb: n_high x n_trk cosine
+ * distances max(0, 1 - u.v / (|u| |v|)); cost: -(asso + angle) + 1.3 emb. */
+int yta_hybridsort_debug_costs_enable(yta_hybridsort *engine, int on);
+int yta_hybridsort_debug_costs(yta_hybridsort *engine, int stream, int *dims, int *rows,
+                               long long *ids, double *boxes, double *emb, double *cost);
 /* HybridSORT Kalman KAT (hybridsort.py:112-320): n tracks initialised from rows b0 (n x 5:
  * x1 y1 x2 y2 score) run `steps` steps of predict (velocity clamp) + update(b[step] (n x 5); a
  * NaN first value = update(None)) with the freeze / unfreeze replay; final x (n x 9) and full P

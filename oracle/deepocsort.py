@@ -253,8 +253,16 @@ def aw_max_metric(emb_cost, w_emb, bottom=0.5):
 
 
 def associate_emb(dets, trks, func, thr, velocities, prev_obs, inertia, w, h, emb_cost, w_emb,
-                  aw_off, aw_param):
-    """association.py:111-201 with the embedding term."""
+                  aw_off, aw_param, rec=None):
+    """association.py:111-201 with the embedding term.
+
+    rec: an optional dict that receives what the call computes, matrices detections x trackers:
+    iou, cos (the clipped cosine of the angle term), valid (per tracker), scores (per detection),
+    angle_cost, emb_raw (emb_cost before the in-place zeroing; None without embeddings), emb_term
+    (after zeroing and AW or * w_emb; 0 without embeddings), cost (what linear_assignment_padded
+    gets), matched (the pairs before the threshold filter) and shortcut.  On the frames that take
+    the unique-match shortcut emb_term and cost are computed the same way from a copy.  Without
+    trackers it receives nothing."""
     if len(trks) == 0:
         return np.empty((0, 2), dtype=int), np.arange(len(dets)), np.empty((0, 5), dtype=int)
     t = prev_obs[..., np.newaxis]
@@ -272,10 +280,24 @@ def associate_emb(dets, trks, func, thr, velocities, prev_obs, inertia, w, h, em
     scores = np.repeat(dets[:, -1][:, np.newaxis], trks.shape[0], axis=1)
     valid = np.repeat(valid[:, np.newaxis], X.shape[1], axis=1)
     angle_cost = ((valid * ang) * inertia).T * scores
+    if rec is not None:
+        rec.update(iou=iou.copy(), cos=cos.T.copy(), valid=1.0 - (prev_obs[:, 4] < 0),
+                   scores=dets[:, -1].copy(), angle_cost=angle_cost.copy(),
+                   emb_raw=None if emb_cost is None else emb_cost.copy(), shortcut=False)
     if min(iou.shape):
         a = (iou > thr).astype(np.int32)
         if a.sum(1).max() == 1 and a.sum(0).max() == 1:
             matched = np.stack(np.where(a), axis=1)
+            if rec is not None:   # the cost this frame never needed, from a copy
+                term = 0
+                if emb_cost is not None:
+                    term = emb_cost.copy()
+                    term[iou <= 0] = 0
+                    if not aw_off:
+                        term = aw_max_metric(term, w_emb, bottom=aw_param)
+                    else:
+                        term *= w_emb
+                rec.update(emb_term=term, cost=-(iou + angle_cost + term), shortcut=True)
         else:
             if emb_cost is None:
                 emb_cost = 0
@@ -285,11 +307,18 @@ def associate_emb(dets, trks, func, thr, velocities, prev_obs, inertia, w, h, em
                     emb_cost = aw_max_metric(emb_cost, w_emb, bottom=aw_param)
                 else:
                     emb_cost *= w_emb
+            if rec is not None:
+                rec.update(emb_term=np.array(emb_cost, copy=True),
+                           cost=-(iou + angle_cost + emb_cost))
             matched = linear_assignment_padded(-(iou + angle_cost + emb_cost))
             if matched.size == 0:
                 matched = np.empty(shape=(0, 2))
     else:
         matched = np.empty(shape=(0, 2))
+        if rec is not None:
+            rec.update(emb_term=0, cost=-(iou + angle_cost))
+    if rec is not None:
+        rec["matched"] = np.array(matched, dtype=np.int64).reshape(-1, 2)
     u_det = [d for d in range(len(dets)) if d not in matched[:, 0]]
     u_trk = [k for k in range(len(trks)) if k not in matched[:, 1]]
     matches = []
@@ -315,6 +344,10 @@ class DeepOCSortOracle:
         self.w_emb, self.af, self.aw_param = w_association_emb, alpha_fixed_emb, aw_param
         self.embedding_off, self.cmc_off, self.aw_off = embedding_off, cmc_off, aw_off
         self.count = 1                                           # :347
+        self.recorder = None       # a list: one dict per update() (associate_emb's rec, det_rows,
+                                   # dets, trks, dets_embs, trk_ids, trk_embs as stacked for the
+                                   # product);
+                                   # outputs are the same with and without it
 
     def update(self, dets, img_shape, feats=None, warp=None):
         """dets (M, 6); feats: get_features' rows for the detections with conf > det_thresh;
@@ -355,9 +388,17 @@ class DeepOCSortOracle:
             emb_cost = None
         else:
             emb_cost = dets_embs @ trk_embs.T
+        rec = None
+        if self.recorder is not None:
+            rec = dict(det_rows=dets[:, 6].astype(np.int64), dets=dets[:, 0:5].copy(),
+                       trks=np.array(trks[:, :4], dtype=np.float64).reshape(-1, 4),
+                       dets_embs=np.array(dets_embs, copy=True),
+                       trk_ids=np.array([t.id for t in self.trackers], dtype=np.int64),
+                       trk_embs=np.array(trk_embs, copy=True))
+            self.recorder.append(rec)
         matched, u_det, u_trk = associate_emb(dets[:, 0:5], trks, self.func, self.thr, vel, k_obs,
                                               self.inertia, w, h, emb_cost, self.w_emb,
-                                              self.aw_off, self.aw_param)
+                                              self.aw_off, self.aw_param, rec=rec)
         for m in matched:
             self.trackers[m[1]].update(dets[m[0], :])
             self.trackers[m[1]].update_emb(dets_embs[m[0]], dets_alpha[m[0]])

@@ -249,11 +249,14 @@ def embedding_distance(tf, df):
     return np.maximum(0.0, cdist(tf, df, "cosine"))
 
 
-def cost_vel(Y, X, vel, dets, prev_obs, vdc_weight, n_trk):
-    """association.py:314-335."""
+def cost_vel(Y, X, vel, dets, prev_obs, vdc_weight, n_trk, cos_out=None):
+    """association.py:314-335.  cos_out: an optional list that receives the clipped cosines
+    (detections x trackers)."""
     iy = np.repeat(vel[:, 0][:, np.newaxis], Y.shape[1], axis=1)
     ix = np.repeat(vel[:, 1][:, np.newaxis], X.shape[1], axis=1)
     cos = np.clip(ix * X + iy * Y, a_min=-1, a_max=1)
+    if cos_out is not None:
+        cos_out.append(cos.T.copy())
     ang = (np.pi / 2.0 - np.abs(np.arccos(cos))) / np.pi
     valid = np.ones(prev_obs.shape[0])
     valid[np.where(prev_obs[:, 4] < 0)] = 0
@@ -272,25 +275,40 @@ def corner_dirs(dets, prev_obs, cx, cy):
 
 
 def associate_reid(dets, trks, func, thr, vels, prev_obs, inertia, emb_cost, w_emb=1.3,
-                   corr_thresh=0.4):
+                   corr_thresh=0.4, rec=None):
     """associate_4_points_with_score_with_reid (association.py:495-581) as HybridSORT calls it
-    (TCM weight 0, weights (1.0, 1.3), long-term weight 0, correction on)."""
+    (TCM weight 0, weights (1.0, 1.3), long-term weight 0, correction on).
+
+    rec: an optional dict that receives what the call computes, matrices detections x trackers:
+    iou, cos (the four corners' clipped cosines), corner_costs (their four angle terms), valid
+    (per tracker), scores (per detection), angle_cost (the four summed), emb_cost (the cosine
+    distances handed in), cost (what linear_assignment_padded gets) and matched (the pairs before
+    the correction filter).  Without trackers it
+    receives nothing."""
     if len(trks) == 0:
         return np.empty((0, 2), dtype=int), np.arange(len(dets)), np.empty((0, 5), dtype=int)
     costs = []
+    cos_out = None if rec is None else []
     for k, (cx, cy) in enumerate(CORNERS):
         Y, X = corner_dirs(dets, prev_obs, cx, cy)
-        costs.append(cost_vel(Y, X, vels[k], dets, prev_obs, inertia, trks.shape[0]))
+        costs.append(cost_vel(Y, X, vels[k], dets, prev_obs, inertia, trks.shape[0], cos_out))
     iou = func(dets, trks)
     score_dif = np.abs(trks[np.newaxis, :, 4] - dets[:, np.newaxis, 4])
     angle = costs[0] + costs[1] + costs[2] + costs[3]
     angle -= score_dif * 0
+    if rec is not None:
+        rec.update(iou=iou.copy(), cos=cos_out, corner_costs=[c.copy() for c in costs],
+                   valid=1.0 - (prev_obs[:, 4] < 0), scores=dets[:, -1].copy(),
+                   angle_cost=angle.copy(), emb_cost=np.array(emb_cost, copy=True),
+                   cost=1.0 * (-(iou + angle)) + w_emb * emb_cost + 0.0)
     if min(iou.shape) > 0:
         matched = linear_assignment_padded(1.0 * (-(iou + angle)) + w_emb * emb_cost + 0.0)
         if matched.size == 0:
             matched = np.empty(shape=(0, 2))
     else:
         matched = np.empty(shape=(0, 2))
+    if rec is not None:
+        rec["matched"] = np.array(matched, dtype=np.int64).reshape(-1, 2)
     u_det = [d for d in range(len(dets)) if d not in matched[:, 0]]
     u_trk = [t for t in range(len(trks)) if t not in matched[:, 1]]
     thre = iou - score_dif
@@ -316,6 +334,9 @@ class HybridSortOracle:
         self.det_thresh, self.delta_t, self.inertia = det_thresh, delta_t, inertia
         self.func = ASSO[asso_func]
         self.count = 0                                           # :361
+        self.recorder = None       # a list: one dict per update() (associate_reid's rec, det_rows,
+                                   # dets, trks, dets_embs, trk_ids, trk_feats); outputs are the
+                                   # same with and without it
 
     def update(self, dets, feats):
         """dets (M, 6) [x1, y1, x2, y2, conf, cls]; feats: get_features' (M, D) float32 rows
@@ -350,8 +371,16 @@ class HybridSortOracle:
         emb = embedding_distance(tf, feat_keep).T
         if len(self.trackers):
             vels = [v.reshape(len(self.trackers), 2) for v in vels]
+        rec = None
+        if self.recorder is not None:
+            rec = dict(det_rows=np.flatnonzero(remain).astype(np.int64), dets=dets5.copy(),
+                       trks=np.array(trks[:, :4], dtype=np.float64).reshape(-1, 4),
+                       dets_embs=feat_keep.copy(),
+                       trk_ids=np.array([t.id for t in self.trackers], dtype=np.int64),
+                       trk_feats=[np.array(t.smooth_feat, copy=True) for t in self.trackers])
+            self.recorder.append(rec)
         matched, u_det, u_trk = associate_reid(dets5, trks, self.func, self.thr, vels, k_obs,
-                                               self.inertia, emb)
+                                               self.inertia, emb, rec=rec)
         for m in matched:
             self.trackers[m[1]].update(dets5[m[0], :], dets0[m[0], 5], dets0[m[0], 6],
                                        feat_keep[m[0], :])

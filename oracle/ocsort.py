@@ -192,8 +192,14 @@ def _asso(func, a, b, w, h):
     return func(a, b)
 
 
-def associate(dets, trks, func, thr, velocities, prev_obs, inertia, w, h):
-    """association.py:111-201 (no embedding term)."""
+def associate(dets, trks, func, thr, velocities, prev_obs, inertia, w, h, rec=None):
+    """association.py:111-201 (no embedding term).
+
+    rec: an optional dict that receives what the call computes, matrices detections x trackers:
+    iou, cos (the clipped cosine of the angle term), valid (per tracker), scores (per detection),
+    angle_cost, cost (what linear_assignment_padded gets, computed on the frames that take the
+    unique-match shortcut as well), matched (the pairs before the threshold filter) and shortcut.
+    Without trackers it receives nothing."""
     if len(trks) == 0:
         return np.empty((0, 2), dtype=int), np.arange(len(dets)), np.empty((0, 5), dtype=int)
     # speed_direction_batch (:8-17): track k-obs -> det direction, (num_track, num_det)
@@ -212,16 +218,24 @@ def associate(dets, trks, func, thr, velocities, prev_obs, inertia, w, h):
     scores = np.repeat(dets[:, -1][:, np.newaxis], trks.shape[0], axis=1)
     valid = np.repeat(valid[:, np.newaxis], X.shape[1], axis=1)
     angle_cost = ((valid * ang) * inertia).T * scores
+    if rec is not None:
+        rec.update(iou=iou.copy(), cos=cos.T.copy(), valid=1.0 - (prev_obs[:, 4] < 0),
+                   scores=dets[:, -1].copy(), angle_cost=angle_cost.copy(),
+                   cost=-(iou + angle_cost + 0), shortcut=False)
     if min(iou.shape):
         a = (iou > thr).astype(np.int32)
         if a.sum(1).max() == 1 and a.sum(0).max() == 1:
             matched = np.stack(np.where(a), axis=1)
+            if rec is not None:
+                rec["shortcut"] = True
         else:
             matched = linear_assignment_padded(-(iou + angle_cost + 0))
             if matched.size == 0:
                 matched = np.empty(shape=(0, 2))
     else:
         matched = np.empty(shape=(0, 2))
+    if rec is not None:
+        rec["matched"] = np.array(matched, dtype=np.int64).reshape(-1, 2)
     u_det = [d for d in range(len(dets)) if d not in matched[:, 0]]
     u_trk = [k for k in range(len(trks)) if k not in matched[:, 1]]
     matches = []
@@ -245,6 +259,8 @@ class OCSortOracle:
         self.func = ASSO[asso_func]
         self.use_byte = use_byte
         self.count = 0                                          # KalmanBoxTracker.count (:216)
+        self.recorder = None       # a list: one dict per update() (associate's rec, det_rows,
+                                   # dets, trks, trk_ids); outputs are the same with and without it
 
     def update(self, dets, img_shape):
         """dets (M, 6); img_shape: img.shape (only h, w are read, :239)."""
@@ -270,8 +286,14 @@ class OCSortOracle:
         last_boxes = np.array([t.last_obs for t in self.trackers])
         k_obs = np.array([t.k_previous_obs() for t in self.trackers])
         # first round (:279-284)
+        rec = None
+        if self.recorder is not None:
+            rec = dict(det_rows=dets[:, 6].astype(np.int64), dets=dets[:, 0:5].copy(),
+                       trks=np.array(trks[:, :4], dtype=np.float64).reshape(-1, 4),
+                       trk_ids=np.array([t.id for t in self.trackers], dtype=np.int64))
+            self.recorder.append(rec)
         matched, u_det, u_trk = associate(dets[:, 0:5], trks, self.func, self.thr, vel, k_obs,
-                                          self.inertia, w, h)
+                                          self.inertia, w, h, rec=rec)
         for m in matched:
             self.trackers[m[1]].update(dets[m[0]])
         # BYTE round (:289-313)

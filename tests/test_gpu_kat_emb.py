@@ -6,7 +6,12 @@ aw_metric), through the C ABI.
   dot products are summed in a different order than SciPy's loop).
 * yta_aw_max_metric (association.py:79-108, the DeepOCSORT engine's top2_push / aw_weight) against
   oracle/deepocsort.aw_max_metric: bit-exact (top-2 selection is order-free and the weight
-  expression is the reference's)."""
+  expression is the reference's).
+
+These are kat.hip's stand-alone kernels (k_emb_dist, k_aw_weights, k_aw_apply): serial, one thread
+per row or column, sharing only top2_push, aw_weight and cosine_dist16 with the engines.  The
+kernels the engines run (k_doc_emb, k_doc_emb_pairs, k_doc_aw, k_doc_aw_cols, k_doc_final,
+k_doc_cost, k_oc_cost, k_hs_emb) are compared entry by entry in tests/test_gpu_oc_costs.py."""
 import numpy as np
 import pytest
 from scipy.spatial.distance import cdist

@@ -184,6 +184,8 @@ _SIGS = {
     "yta_ocsort_stats": ([_P, _P], _I),
     "yta_ocsort_lap_stats": ([_P, _P, _I], _I),
     "yta_ocsort_hip_stream": ([_P, _P], _I),
+    "yta_ocsort_debug_costs_enable": ([_P, _I], _I),
+    "yta_ocsort_debug_costs": ([_P, _I, _P, _P, _P, _P, _P, _P], _I),
     "yta_kf7_run": ([_I, _I, _I, _P, _P, _P, _P], _I),
     "yta_deepocsort_create": ([_I, _I, _I, _I, _I, _P, _P], _I),
     "yta_deepocsort_destroy": ([_P], _I),
@@ -199,6 +201,8 @@ _SIGS = {
     "yta_deepocsort_stats": ([_P, _P], _I),
     "yta_deepocsort_lap_stats": ([_P, _P, _I], _I),
     "yta_deepocsort_hip_stream": ([_P, _P], _I),
+    "yta_deepocsort_debug_costs_enable": ([_P, _I], _I),
+    "yta_deepocsort_debug_costs": ([_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "yta_kf8_run": ([_I, _I, _I, _P, _P, _P, _P, _P], _I),
     "yta_hybridsort_create": ([_I, _I, _I, _I, _I, _P, _P], _I),
     "yta_hybridsort_destroy": ([_P], _I),
@@ -215,6 +219,8 @@ _SIGS = {
     "yta_hybridsort_stats": ([_P, _P], _I),
     "yta_hybridsort_lap_stats": ([_P, _P, _I], _I),
     "yta_hybridsort_hip_stream": ([_P, _P], _I),
+    "yta_hybridsort_debug_costs_enable": ([_P, _I], _I),
+    "yta_hybridsort_debug_costs": ([_P, _I, _P, _P, _P, _P, _P, _P], _I),
     "yta_kf9_run": ([_I, _I, _I, _P, _P, _P, _P], _I),
     "yta_strongsort_create": ([_I, _I, _I, _I, _I, _I, _P, _P], _I),
     "yta_strongsort_destroy": ([_P], _I),

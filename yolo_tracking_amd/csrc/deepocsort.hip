@@ -1207,6 +1207,22 @@ struct yta_deepocsort : OcEngine<DocBuf, yta_deepocsort_params> {   // the skele
     void launch_reset(int s0, int n) {
         hipLaunchKernelGGL(k_doc_reset, dim3(n), dim3(256), 0, stream, b.a, s0);
     }
+    // the stage-1 snapshot (oc_debug_snapshot): ODB_MAT asso, then cost, emat, rw, cw
+    long long mat_stride() const { return (long long)std::max(b.a.MAXD, 4) * b.a.CAP; }
+    std::vector<OcDebugSrc> debug_sources() const {
+        const DocArgs &a = b.a;
+        const size_t sc = (size_t)S * a.CAP, mat = sizeof(double) * S * mat_stride();
+        return {{a.cnt, sizeof(DocCounters) * S, 1, 0},
+                {a.hi_row, sizeof(int) * S * a.MAXD, 1, 0},
+                {a.cslot, sizeof(int) * sc, 1, 0},
+                {&a.rec[0].id, sizeof(long long), sc, sizeof(DocTrack)},
+                {a.cbox, sizeof(Box) * sc, 1, 0},
+                {a.mat, mat, 1, 0},
+                {a.mat2, mat, 1, 0},
+                {a.emat, mat, 1, 0},
+                {a.rw, sizeof(double) * S * a.MAXD, 1, 0},
+                {a.cw, sizeof(double) * sc, 1, 0}};
+    }
 };
 
 int yta_deepocsort::alloc(int cap, int maxd, DocBuf &b) const {
@@ -1340,6 +1356,10 @@ int doc_launch(yta_deepocsort *e, const double *d_dets, const int *d_off, const 
     }
     hipLaunchKernelGGL(k_doc_final, gm, dim3(256), 0, e->stream, a);
     YTA_HIP(hipGetLastError());
+    if (e->dbg.on) {   // tests: the matrices before the solver and the OCR round
+        const int drc = oc_debug_snapshot(e);
+        if (drc) return drc;
+    }
     {
         const long long rows = (a.MAXD + OC_T / WAVE - 1) / (OC_T / WAVE);
         const long long rcap = std::max<long long>(4, 4096 / a.S);
@@ -1576,6 +1596,28 @@ int yta_kf8_run(int device, int n, int steps, const double *b0, const double *b,
 
 int yta_deepocsort_lap_stats(yta_deepocsort *e, long long *stats, int n) {
     return oc_lap_stats(e, stats, n);
+}
+int yta_deepocsort_debug_costs_enable(yta_deepocsort *e, int on) {
+    return oc_debug_enable(e, on);
+}
+int yta_deepocsort_debug_costs(yta_deepocsort *e, int stream, int *dims, int *rows,
+                               long long *ids, double *boxes, double *asso, double *emb,
+                               double *rw, double *cw, double *cost) {
+    YTA_CHECK(e && dims, YTA_ERR_INVALID, "null argument");
+    DocCounters c;
+    int rc = oc_debug_head(e, stream, &c, rows, ids, boxes);
+    if (rc) return rc;
+    dims[0] = c.n_high;
+    dims[1] = c.n_trk;
+    dims[2] = c.n_pos;
+    dims[3] = c.col_ovf;
+    const long long mb = stream * e->mat_stride(), n = (long long)c.n_high * c.n_trk;
+    rc = oc_debug_fetch(e, ODB_MAT, mb, n, asso);
+    if (!rc) rc = oc_debug_fetch(e, ODB_MAT + 1, mb, n, cost);
+    if (!rc) rc = oc_debug_fetch(e, ODB_MAT + 2, mb, n, emb);
+    if (!rc) rc = oc_debug_fetch(e, ODB_MAT + 3, (long long)stream * e->dbg.maxd, c.n_high, rw);
+    if (!rc) rc = oc_debug_fetch(e, ODB_MAT + 4, (long long)stream * e->dbg.cap, c.n_trk, cw);
+    return rc;
 }
 int yta_deepocsort_hip_stream(yta_deepocsort *e, void **stream) {
     return oc_hip_stream(e, stream);

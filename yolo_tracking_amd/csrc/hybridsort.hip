@@ -1122,6 +1122,22 @@ struct yta_hybridsort : OcEngine<HsBuf, yta_hybridsort_params> {   // the skelet
     void launch_reset(int s0, int n) {
         hipLaunchKernelGGL(k_hs_reset, dim3(n), dim3(256), 0, stream, b.a, s0);
     }
+    // the stage-1 snapshot (oc_debug_snapshot): ODB_MAT emat (cosine distance), ODB_MAT + 1 cost
+    long long mat_stride() const {
+        return std::max<long long>(b.a.MAXD, 4) * b.a.CAP;   // hs_mb
+    }
+    std::vector<OcDebugSrc> debug_sources() const {
+        const HsArgs &a = b.a;
+        // the last stream's matrix ends at S * hs_mb's stride at the latest (alloc's is no smaller)
+        const size_t sc = (size_t)S * a.CAP, mat = sizeof(double) * S * mat_stride();
+        return {{a.cnt, sizeof(HsCounters) * S, 1, 0},
+                {a.hi_row, sizeof(int) * S * a.MAXD, 1, 0},
+                {a.cslot, sizeof(int) * sc, 1, 0},
+                {&a.rec[0].id, sizeof(long long), sc, sizeof(HsTrack)},
+                {a.col[0].box, sizeof(double) * 4, sc, sizeof(HsCol)},
+                {a.emat, mat, 1, 0},
+                {a.cost, mat, 1, 0}};
+    }
 };
 
 int yta_hybridsort::alloc(int cap, int maxd, HsBuf &b) const {
@@ -1220,6 +1236,10 @@ int hs_launch(yta_hybridsort *e, const double *d_dets, const int *d_off, const f
         default: hipLaunchKernelGGL(k_hs_emb<4>, ge, dim3(256), 0, e->stream, a); break;
     }
     YTA_HIP(hipGetLastError());
+    if (e->dbg.on) {   // tests: the matrices before the solver and the OCR round
+        const int drc = oc_debug_snapshot(e);
+        if (drc) return drc;
+    }
     {
         const long long rows = (a.MAXD + OC_T / WAVE - 1) / (OC_T / WAVE);
         const long long rcap = std::max<long long>(4, 4096 / a.S);
@@ -1449,6 +1469,22 @@ int yta_kf9_run(int device, int n, int steps, const double *b0, const double *b,
 
 int yta_hybridsort_lap_stats(yta_hybridsort *e, long long *stats, int n) {
     return oc_lap_stats(e, stats, n);
+}
+int yta_hybridsort_debug_costs_enable(yta_hybridsort *e, int on) {
+    return oc_debug_enable(e, on);
+}
+int yta_hybridsort_debug_costs(yta_hybridsort *e, int stream, int *dims, int *rows,
+                               long long *ids, double *boxes, double *emb, double *cost) {
+    YTA_CHECK(e && dims, YTA_ERR_INVALID, "null argument");
+    HsCounters c;
+    int rc = oc_debug_head(e, stream, &c, rows, ids, boxes);
+    if (rc) return rc;
+    dims[0] = c.n_high;
+    dims[1] = c.n_trk;
+    const long long mb = stream * e->mat_stride(), n = (long long)c.n_high * c.n_trk;
+    rc = oc_debug_fetch(e, ODB_MAT, mb, n, emb);
+    if (!rc) rc = oc_debug_fetch(e, ODB_MAT + 1, mb, n, cost);
+    return rc;
 }
 int yta_hybridsort_hip_stream(yta_hybridsort *e, void **stream) {
     return oc_hip_stream(e, stream);

@@ -134,6 +134,31 @@ struct OcTensorState {
     long long stat[4] = {};              // frames, host_waits, reserves, ingest_skipped
 };
 
+// Test-only snapshot of the stage-1 matrices (yta_<t>_debug_costs), which later rounds of the
+// frame overwrite.  Off unless enabled; when on, the engine's launch calls oc_debug_snapshot after
+// its last cost kernel and before its first solver kernel, and every source of the engine's
+// debug_sources() is copied device to device on the engine's stream.
+struct OcDebugSrc {   // `rows` rows of `width` bytes, `pitch` bytes apart; copied densely
+    const void *src;
+    size_t width, rows, pitch;
+};
+// the first five sources of every engine (ODB_BOX: the predicted boxes, 4 doubles per tracker in
+// column order), its matrices from ODB_MAT on
+enum { ODB_CNT, ODB_ROWS, ODB_SLOT, ODB_ID, ODB_BOX, ODB_MAT };
+struct OcDebugCosts {
+    bool on = false, taken = false;
+    int cap = 0, maxd = 0;        // the engine's sizes when the snapshot was taken
+    std::vector<void *> dev;      // one dense copy per source
+    std::vector<size_t> bytes;    // their sizes
+    void release() {
+        for (void *p : dev)
+            if (p) (void)hipFree(p);
+        dev.clear();
+        bytes.clear();
+        taken = false;
+    }
+};
+
 template <typename BufT, typename ParamsT>
 struct OcEngine {
     using Buf = BufT;
@@ -148,6 +173,7 @@ struct OcEngine {
     long long feat_cap = 0;
     StreamMask mask;   // stream-subset updates (subset.hpp)
     OcTensorState t;   // the tensor path (oc_update_tensors)
+    OcDebugCosts dbg;  // the stage-1 snapshot (oc_debug_snapshot), off by default
 };
 
 // One per-slot array of a growth: S rows of `bytes` per slot, CAP slots a row.
@@ -359,6 +385,104 @@ int oc_end_frame(E *e, long long *next_id, double *out, int out_capacity, int *o
     return YTA_OK;
 }
 
+// ------------------------------------------------------------------ stage-1 snapshot (tests)
+template <typename E>
+int oc_debug_enable(E *e, int on) {
+    YTA_CHECK(e, YTA_ERR_INVALID, "null engine");
+    YTA_HIP(hipSetDevice(e->device));
+    YTA_HIP(host_wait(e->stream));
+    e->dbg.on = on != 0;
+    if (!on) e->dbg.release();
+    return YTA_OK;
+}
+
+// The engine's launch, with e->dbg.on, between its last cost kernel and its first solver kernel.
+template <typename E>
+int oc_debug_snapshot(E *e) {
+    OcDebugCosts &g = e->dbg;
+    const std::vector<OcDebugSrc> src = e->debug_sources();
+    g.taken = false;
+    g.dev.resize(src.size(), nullptr);
+    g.bytes.resize(src.size(), 0);
+    for (size_t k = 0; k < src.size(); ++k) {
+        const size_t need = src[k].width * src[k].rows;
+        if (g.bytes[k] != need || !g.dev[k]) {   // first use, or the engine has grown
+            if (g.dev[k]) (void)hipFree(g.dev[k]);
+            g.dev[k] = nullptr;
+            g.bytes[k] = 0;
+            YTA_HIP(hipMalloc(&g.dev[k], std::max<size_t>(need, 8)));
+            g.bytes[k] = need;
+        }
+        if (!need) continue;
+        if (src[k].rows == 1)
+            YTA_HIP(hipMemcpyAsync(g.dev[k], src[k].src, need, hipMemcpyDeviceToDevice, e->stream));
+        else
+            YTA_HIP(hipMemcpy2DAsync(g.dev[k], src[k].width, src[k].src, src[k].pitch,
+                                     src[k].width, src[k].rows, hipMemcpyDeviceToDevice,
+                                     e->stream));
+    }
+    g.cap = e->b.a.CAP;
+    g.maxd = e->b.a.MAXD;
+    g.taken = true;
+    return YTA_OK;
+}
+
+// Waits for the engine's stream.  *c: the counters of `stream` as the snapshot took them (n_high
+// x n_trk is the matrix); rows: the input row of each matrix row; ids, boxes: the track id and
+// the predicted box (x1, y1, x2, y2) of each matrix column (each may be null).
+template <typename E>
+int oc_debug_head(E *e, int stream, typename E::Buf::Counters *c, int *rows, long long *ids,
+                  double *boxes) {
+    using Counters = typename E::Buf::Counters;
+    YTA_CHECK(e && c, YTA_ERR_INVALID, "null argument");
+    YTA_CHECK(stream >= 0 && stream < e->S, YTA_ERR_INVALID, "bad stream %d", stream);
+    const OcDebugCosts &g = e->dbg;
+    YTA_CHECK(g.on && g.taken, YTA_ERR_INVALID,
+              "no stage-1 snapshot: enable debug costs, then update");
+    YTA_HIP(hipSetDevice(e->device));
+    YTA_HIP(host_wait(e->stream));
+    YTA_HIP(hipMemcpy(c, static_cast<const Counters *>(g.dev[ODB_CNT]) + stream, sizeof(Counters),
+                      hipMemcpyDeviceToHost));
+    YTA_CHECK(c->n_high >= 0 && c->n_high <= g.maxd && c->n_trk >= 0 && c->n_trk <= g.cap,
+              YTA_ERR_HIP, "snapshot sizes %d x %d outside %d x %d", c->n_high, c->n_trk, g.maxd,
+              g.cap);
+    if (rows && c->n_high)
+        YTA_HIP(hipMemcpy(rows, static_cast<const int *>(g.dev[ODB_ROWS]) + (size_t)stream * g.maxd,
+                          sizeof(int) * c->n_high, hipMemcpyDeviceToHost));
+    if (ids && c->n_trk) {
+        std::vector<int> slot(c->n_trk);
+        std::vector<long long> id(g.cap);
+        YTA_HIP(hipMemcpy(slot.data(),
+                          static_cast<const int *>(g.dev[ODB_SLOT]) + (size_t)stream * g.cap,
+                          sizeof(int) * c->n_trk, hipMemcpyDeviceToHost));
+        YTA_HIP(hipMemcpy(id.data(),
+                          static_cast<const long long *>(g.dev[ODB_ID]) + (size_t)stream * g.cap,
+                          sizeof(long long) * g.cap, hipMemcpyDeviceToHost));
+        for (int j = 0; j < c->n_trk; ++j) {
+            YTA_CHECK(slot[j] >= 0 && slot[j] < g.cap, YTA_ERR_HIP, "snapshot slot %d", slot[j]);
+            ids[j] = id[slot[j]];
+        }
+    }
+    if (boxes && c->n_trk)
+        YTA_HIP(hipMemcpy(boxes,
+                          static_cast<const double *>(g.dev[ODB_BOX]) + (size_t)stream * g.cap * 4,
+                          sizeof(double) * 4 * c->n_trk, hipMemcpyDeviceToHost));
+    return YTA_OK;
+}
+
+// n elements of source k from element `first` on (after oc_debug_head, which waited); dst may be
+// null (nothing is read).
+template <typename T, typename E>
+int oc_debug_fetch(E *e, int k, long long first, long long n, T *dst) {
+    const OcDebugCosts &g = e->dbg;
+    if (!dst || n <= 0) return YTA_OK;
+    YTA_CHECK((size_t)(first + n) * sizeof(T) <= g.bytes[k], YTA_ERR_HIP,
+              "snapshot read past source %d", k);
+    YTA_HIP(hipMemcpy(dst, static_cast<const T *>(g.dev[k]) + first, sizeof(T) * n,
+                      hipMemcpyDeviceToHost));
+    return YTA_OK;
+}
+
 // ------------------------------------------------------------------ the tensor path
 // yta_<t>_update_tensors: device rows in, device rows out, stream-ordered.  The protocol is
 // tensor_path.hpp's: the frame runs on the engine's stream as plain launches (k_tp_ingest, the
@@ -420,6 +544,8 @@ int oc_update_tensors(E *e, void *caller_stream, const void *d_dets, int dtype,
                                d_row_offsets, &total);
     if (rc) return rc;
     YTA_CHECK(img_wh || e->prm.asso_func != 4, YTA_ERR_INVALID, "centroid needs img_wh");
+    YTA_CHECK(!e->dbg.on, YTA_ERR_INVALID,
+              "debug costs are on: the tensor path takes no stage-1 snapshot");
     const int S = e->S, D = e->D;
     YTA_HIP(hipSetDevice(e->device));
     const hipStream_t cs = (hipStream_t)caller_stream;
@@ -529,6 +655,7 @@ int oc_destroy(E *e) {
     if (e->stream) (void)host_wait(e->stream);
     e->b.release();
     e->mask.release();
+    e->dbg.release();
     e->t.ring.release();
     tensor_free_retired(e->t.retired);
     for (void *d : {(void *)e->t.det, (void *)e->t.off, (void *)e->t.wh, (void *)e->t.feat})

@@ -682,6 +682,19 @@ struct yta_ocsort : OcEngine<OcBuf, yta_ocsort_params> {   // the skeleton: oc_h
     void launch_reset(int s0, int n) {
         hipLaunchKernelGGL(k_oc_reset, dim3(n), dim3(256), 0, stream, b.a, s0);
     }
+    // the stage-1 snapshot (oc_debug_snapshot): ODB_MAT asso, ODB_MAT + 1 cost
+    long long mat_stride() const { return (long long)std::max(b.a.MAXD, 4) * b.a.CAP; }
+    std::vector<OcDebugSrc> debug_sources() const {
+        const OcArgs &a = b.a;
+        const size_t sc = (size_t)S * a.CAP, mat = sizeof(double) * S * mat_stride();
+        return {{a.cnt, sizeof(OcCounters) * S, 1, 0},
+                {a.hi_row, sizeof(int) * S * a.MAXD, 1, 0},
+                {a.list, sizeof(int) * sc, 1, 0},
+                {&a.rec[0].id, sizeof(long long), sc, sizeof(OcTrack)},
+                {a.cbox, sizeof(Box) * sc, 1, 0},
+                {a.mat, mat, 1, 0},
+                {a.mat2, mat, 1, 0}};
+    }
 };
 
 int yta_ocsort::alloc(int cap, int maxd, OcBuf &b) const {
@@ -768,6 +781,10 @@ int oc_launch(yta_ocsort *e, const double *d_dets, const int *d_off, const int *
     hipLaunchKernelGGL(k_oc_cost, dim3((unsigned)std::max<long long>(1, std::min(per, cap)), a.S),
                        dim3(OC_T), 0, e->stream, a);
     YTA_HIP(hipGetLastError());
+    if (e->dbg.on) {   // tests: the matrices before the solver and the later rounds
+        const int drc = oc_debug_snapshot(e);
+        if (drc) return drc;
+    }
     const long long rows = (a.MAXD + OC_T / WAVE - 1) / (OC_T / WAVE);
     hipLaunchKernelGGL(k_oc_rowpre, dim3((unsigned)std::max<long long>(1, std::min(rows, cap)), a.S),
                        dim3(OC_T), 0, e->stream, a);
@@ -909,6 +926,21 @@ int yta_ocsort_lap_stats(yta_ocsort *e, long long *stats, int n) {
     return oc_lap_stats(e, stats, n);
 }
 int yta_ocsort_hip_stream(yta_ocsort *e, void **stream) { return oc_hip_stream(e, stream); }
+
+int yta_ocsort_debug_costs_enable(yta_ocsort *e, int on) { return oc_debug_enable(e, on); }
+int yta_ocsort_debug_costs(yta_ocsort *e, int stream, int *dims, int *rows, long long *ids,
+                           double *boxes, double *asso, double *cost) {
+    YTA_CHECK(e && dims, YTA_ERR_INVALID, "null argument");
+    OcCounters c;
+    int rc = oc_debug_head(e, stream, &c, rows, ids, boxes);
+    if (rc) return rc;
+    dims[0] = c.n_high;
+    dims[1] = c.n_trk;
+    const long long mb = stream * e->mat_stride(), n = (long long)c.n_high * c.n_trk;
+    rc = oc_debug_fetch(e, ODB_MAT, mb, n, asso);
+    if (!rc) rc = oc_debug_fetch(e, ODB_MAT + 1, mb, n, cost);
+    return rc;
+}
 
 #ifdef YTA_STAMPS
 int yta_ocsort_debug_stamps(unsigned long long *out) {

@@ -19,6 +19,7 @@ import inspect
 import numpy as np
 
 from .. import _lib
+from ._debug import DebugCosts
 from ._streams import StreamSubset
 from ._tensors import TensorFrame, TensorPath, is_cuda_tensor, takes_device_frames
 from ..appearance import build_reid
@@ -31,9 +32,26 @@ class KalmanBoxTracker:
     count = 1
 
 
-class DeepOCSortEngine(StreamSubset, TensorPath):
-    """S independent DeepOCSORT streams sharing one device engine."""
+class DeepOCSortEngine(StreamSubset, TensorPath, DebugCosts):
+    """S independent DeepOCSORT streams sharing one device engine.
+
+    debug_costs(stream) (tests; after debug_costs_enable()): `asso`, `emb` (the dot products
+    dets_embs @ trk_embs.T), `cost` = -(asso + angle + embedding term), all n_high x n_trk; the
+    adaptive weights `rw` (n_high) and `cw` (n_trk), defined with embeddings and AW on; `n_pos`
+    and `col_ovf`, the frame's path flags (dense tiles and row scans; dense column scan).  The
+    device defines `emb` only where asso > 0: elsewhere this returns 0, which is exactly the
+    reference's emb_cost[iou_matrix <= 0] = 0 (association.py:165)."""
     _abi = "deepocsort"
+    _debug_fields = (("asso", "m"), ("emb", "m"), ("rw", "r"), ("cw", "c"), ("cost", "m"))
+
+    def debug_costs(self, stream=0):
+        out = super().debug_costs(stream)
+        out["n_pos"], out["col_ovf"] = int(out["dims"][2]), int(out["dims"][3])
+        if self.feat_dim:
+            out["emb"][out["asso"] <= 0] = 0.0
+        else:
+            out["emb"][...] = 0.0
+        return out
 
     def __init__(self, n_streams=1, feat_dim=512, det_thresh=0.3, max_age=30, min_hits=3,
                  iou_threshold=0.3, delta_t=3, asso_func="iou", inertia=0.2,

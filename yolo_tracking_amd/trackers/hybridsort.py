@@ -20,6 +20,7 @@ import ctypes
 import numpy as np
 
 from .. import _lib
+from ._debug import DebugCosts
 from ._streams import StreamSubset
 from ._tensors import TensorFrame, TensorPath
 from ..appearance import build_reid
@@ -31,10 +32,14 @@ class KalmanBoxTracker:
     count = 0
 
 
-class HybridSortEngine(StreamSubset, TensorPath):
+class HybridSortEngine(StreamSubset, TensorPath, DebugCosts):
     """S independent HybridSORT streams sharing one device engine; one update() = one
-    undecorated HybridSORT.update call per stream."""
+    undecorated HybridSORT.update call per stream.
+
+    debug_costs(stream) (tests; after debug_costs_enable()): `emb`, the cosine distances, and
+    `cost` = -(asso + angle) + 1.3 emb, both n_high x n_trk."""
     _abi = "hybridsort"
+    _debug_fields = (("emb", "m"), ("cost", "m"))
 
     def __init__(self, n_streams=1, feat_dim=512, det_thresh=0.0, max_age=30, min_hits=3,
                  iou_threshold=0.3, delta_t=3, asso_func="iou", inertia=0.2, device=0,

@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 
 from .. import _lib
+from ._debug import DebugCosts
 from ._streams import StreamSubset
 from ._tensors import TensorFrame, TensorPath, is_cuda_tensor
 
@@ -21,9 +22,13 @@ class KalmanBoxTracker:
     count = 0
 
 
-class OCSortEngine(StreamSubset, TensorPath):
-    """S independent OCSORT streams sharing one device engine."""
+class OCSortEngine(StreamSubset, TensorPath, DebugCosts):
+    """S independent OCSORT streams sharing one device engine.
+
+    debug_costs(stream) (tests; after debug_costs_enable()): `asso`, the association function's
+    values, and `cost` = -(asso + angle), both n_high x n_trk."""
     _abi = "ocsort"
+    _debug_fields = (("asso", "m"), ("cost", "m"))
 
     def __init__(self, n_streams=1, det_thresh=0.2, max_age=30, min_hits=3, asso_threshold=0.3,
                  delta_t=3, asso_func="iou", inertia=0.2, use_byte=False, device=0,
