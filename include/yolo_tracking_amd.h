@@ -1187,6 +1187,47 @@ int yta_mlfn_subsample(const void *x, int N, int C, int H, int W, int stride, in
 int yta_mlfn_mean2(const void *a, const void *b, long long count, int half, void *y,
                    void *stream);
 
+/* ---- CLIP-ReID ViT (boxmot/appearance/backbones/clip/clip/model.py VisionTransformer,
+ * make_model.py:96-122; appearance/clip.py).  Device pointers, asynchronous on `stream`, float32
+ * (half = 0) or float16 (half = 1) storage, float32 arithmetic, no atomics (the same input gives
+ * the same bits).  Activations are row-major (rows, channels) matrices, a token a row; a row
+ * stride is in elements and at least the row's length, so a call can read or write every L-th
+ * row (token 0 of each sample) or a column slot of a wider buffer.  The necks (make_model.py
+ * :111-112) arrive folded into ln_post's affine and into proj.
+ * yta_clip_linear: y[m][j] = act(sum_k x[m][k] w[j][k] + bias[j]) (+ res[m][j]) for M rows, an
+ * LDS-tiled MFMA GEMM (mfma_f32_32x32x16_f16 / mfma_f32_32x32x2f32, both operand tiles staged in
+ * two LDS buffers).  w in the storage type, Nout rows of K (a Linear's weight as stored; both
+ * operands are then K-contiguous and staged alike), bias float32 or NULL, res in the storage type
+ * or NULL (it may be y), act 0: none, 1: QuickGELU v * sigmoid(1.702 v) (model.py:164-166), ahead
+ * of the residual.  M, K and Nout are arbitrary (> 0).
+ * yta_clip_layernorm: y[m] = (x[m] - mean) / sqrt(var + eps) * gamma + beta over C channels of
+ * each of M rows (model.py:155-161); gamma, beta float32; the mean first, then the biased
+ * variance around it, float32.  y may be x.
+ * yta_clip_patches: x N x 3 x H x W (H, W multiples of 16) -> y (N H/16 W/16) x 768, row
+ * (n, gy, gx), column (c, dy, dx) as conv1.weight.reshape(width, 768) orders them: the patch
+ * embedding (:239-241) is yta_clip_linear on these rows.
+ * yta_clip_tokens: y N x (G + 1) x width = ln_pre(cat(class_embedding, patch rows of sample n) +
+ * positional_embedding) (:242-248); patches N G rows in the storage type; class_embedding
+ * (width), positional_embedding ((G + 1) x width), gamma, beta float32.
+ * yta_clip_attention: nn.MultiheadAttention's core (:183-185) on qkv N x L x 3 width (q | k | v,
+ * head h columns 64 h .. 64 h + 63 of each third): for the first Lq <= L queries of each sample
+ * and head softmax(q k^T / 8) v -> y N x Lq x width, heads concatenated.  head_dim must be 64 and
+ * divide width; L at most 256 (K and V of a head sit in LDS); anything else is YTA_ERR_INVALID.
+ * A query's result has the same bits whatever Lq is. */
+int yta_clip_linear(const void *x, long long x_stride, const void *w, long long w_stride,
+                    const float *bias, const void *res, long long res_stride, int M, int K,
+                    int Nout, int act, int half, void *y, long long y_stride, void *stream);
+int yta_clip_layernorm(const void *x, long long x_stride, long long M, int C, const float *gamma,
+                       const float *beta, float eps, int half, void *y, long long y_stride,
+                       void *stream);
+int yta_clip_patches(const void *x, int N, int H, int W, int half, void *y, void *stream);
+int yta_clip_tokens(const void *patches, long long patch_stride, const float *class_embedding,
+                    const float *positional_embedding, int N, int G, int width,
+                    const float *gamma, const float *beta, float eps, int half, void *y,
+                    void *stream);
+int yta_clip_attention(const void *qkv, int N, int L, int width, int head_dim, int Lq, int half,
+                       void *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

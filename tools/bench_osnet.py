@@ -9,7 +9,9 @@ on MobileNetV2: the HIP forward with the fused expand + depthwise kernel ("fused
 two layers as two launches ("fused": false), and the same folded graph on PyTorch's kernels in
 NHWC and NCHW ("hip_blocks": false), the baseline a model=<torch module> user gets.
 --variant mlfn (appearance/mlfn.py) measures the MLFN HIP forward against the same folded graph on
-PyTorch's kernels (hip=False, "hip_blocks": false) on the same device, float32 and float16."""
+PyTorch's kernels (hip=False, "hip_blocks": false) on the same device, float32 and float16.
+--variant clip (appearance/clip.py) does the same for the CLIP-ReID ViT-B/16, in chunks of
+appearance.clip.CHUNK crops."""
 import argparse
 import json
 import os
@@ -24,18 +26,21 @@ sys.path.insert(0, REPO)
 
 def main():
     ap = argparse.ArgumentParser()
+    from yolo_tracking_amd.appearance.clip import VARIANTS as CLIP
     from yolo_tracking_amd.appearance.mlfn import VARIANTS as MLFN
     from yolo_tracking_amd.appearance.mobilenetv2 import VARIANTS as MBV2
     from yolo_tracking_amd.appearance.osnet import VARIANTS
     ap.add_argument("--variant", default="osnet_x0_25",
-                    choices=sorted(VARIANTS) + sorted(MBV2) + sorted(MLFN),
+                    choices=sorted(VARIANTS) + sorted(MBV2) + sorted(MLFN) + sorted(CLIP),
                     help="OSNet variant (plain, osnet_ibn_* or osnet_ain_*; default osnet_x0_25) "
-                         "or mobilenetv2_x1_0 / mobilenetv2_x1_4, or mlfn")
+                         "or mobilenetv2_x1_0 / mobilenetv2_x1_4, or mlfn, or clip")
     ap.add_argument("--crops", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=10)
     args = ap.parse_args()
     import torch
     from yolo_tracking_amd.appearance import ReIDDetectMultiBackend
+    from yolo_tracking_amd.appearance.clip import CHUNK as CLIP_CHUNK
+    from yolo_tracking_amd.appearance.clip import ClipReID
     from yolo_tracking_amd.appearance.mlfn import MLFNReID
     from yolo_tracking_amd.appearance.mobilenetv2 import MobileNetV2ReID
     from yolo_tracking_amd.appearance.osnet import OSNetReID
@@ -45,8 +50,11 @@ def main():
     wh = rng.uniform(48, 192, (n, 2))
     xy = rng.uniform(0, 1, (n, 2)) * [W - 200, H - 200]
     boxes = np.concatenate([xy, xy + wh], 1)
-    mbv2, mlfn = args.variant in MBV2, args.variant in MLFN
-    if mlfn:   # the HIP forward and the folded graph on PyTorch's kernels, NCHW
+    mbv2, mlfn, clip = args.variant in MBV2, args.variant in MLFN, args.variant in CLIP
+    if clip:   # the HIP forward and the folded graph on PyTorch's kernels, its own chunk
+        configs = [(half, CLIP_CHUNK, hip, False, None) for half in (False, True)
+                   for hip in (True, False)]
+    elif mlfn:   # the HIP forward and the folded graph on PyTorch's kernels, NCHW
         configs = [(half, 1024, hip, False, None) for half in (False, True) for hip in (True, False)]
     elif mbv2:   # (half, chunk, hip, channels_last, fused)
         configs = [(half, 1024, hip, cl, fused) for half in (False, True)
@@ -58,7 +66,9 @@ def main():
             (True, 256, True, False), (False, 1024, False, True), (True, 1024, False, True),
             (True, 1024, False, False))]
     for half, chunk, hip, cl, fused in configs:
-        if mlfn:
+        if clip:
+            net = ClipReID(args.variant, None, device="cuda:0", half=half, chunk=chunk, hip=hip)
+        elif mlfn:
             net = MLFNReID(args.variant, None, device="cuda:0", half=half, chunk=chunk, hip=hip)
         elif mbv2:
             net = MobileNetV2ReID(args.variant, None, device="cuda:0", half=half, chunk=chunk,
@@ -86,7 +96,7 @@ def main():
         for _ in range(args.steps):
             reid.get_features(boxes, img)
         e2e_ms = 1000 * (time.perf_counter() - t0) / args.steps
-        print(json.dumps({"metric": ("MLFN" if mlfn else "MobileNetV2" if mbv2 else "OSNet") +
+        print(json.dumps({"metric": ("CLIP-ReID" if clip else "MLFN" if mlfn else "MobileNetV2" if mbv2 else "OSNet") +
                           " ReID crops/s",
                           "variant": args.variant, "fused": fused,
                           "dtype": "f16" if half else "f32", "crops": n, "chunk": chunk,

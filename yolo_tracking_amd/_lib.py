@@ -301,6 +301,14 @@ _SIGS = {
                       _P, ctypes.c_longlong, _P], _I),
     "yta_mlfn_subsample": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
     "yta_mlfn_mean2": ([_P, _P, ctypes.c_longlong, _I, _P, _P], _I),
+    "yta_clip_linear": ([_P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong,
+                         _I, _I, _I, _I, _I, _P, ctypes.c_longlong, _P], _I),
+    "yta_clip_layernorm": ([_P, ctypes.c_longlong, ctypes.c_longlong, _I, _P, _P, ctypes.c_float,
+                            _I, _P, ctypes.c_longlong, _P], _I),
+    "yta_clip_patches": ([_P, _I, _I, _I, _I, _P, _P], _I),
+    "yta_clip_tokens": ([_P, ctypes.c_longlong, _P, _P, _I, _I, _I, _P, _P, ctypes.c_float, _I,
+                         _P, _P], _I),
+    "yta_clip_attention": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

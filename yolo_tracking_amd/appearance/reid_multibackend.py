@@ -16,7 +16,8 @@ channels-last, batched branches) built from `weights` as the reference builds it
 file name (reid_multibackend.py:57-80): osnet_x0_25 .. osnet_x1_0, and the instance-norm members
 of the family, osnet_ibn_x1_0 and osnet_ain_x1_0 (and their narrower widths), whose norms run in
 csrc/osnet.hip as well, or MobileNetV2 (appearance/mobilenetv2.py: mobilenetv2_x1_0 and
-mobilenetv2_x1_4, csrc/mbv2.hip), or MLFN (appearance/mlfn.py: mlfn, csrc/mlfn.hip); the
+mobilenetv2_x1_4, csrc/mbv2.hip), or MLFN (appearance/mlfn.py: mlfn, csrc/mlfn.hip), or the
+CLIP-ReID ViT-B/16 (appearance/clip.py: clip, csrc/clip.hip; 1280 features); the
 reference's .pt state dicts load unchanged (torch.load(weights_only=True)).  A weight file that is not on disk would be
 downloaded by the reference (gdown, :61-64) or end the program (:67-72); there is no network here,
 so a missing file raises FileNotFoundError.  Freshly initialised weights (benchmarks, plumbing
@@ -107,10 +108,11 @@ class ReIDDetectMultiBackend:
         """reid_multibackend.py:57-80 as a dispatch on the weight file name: the OSNet family
         first (the plain widths, the trackers' default weights, osnet_ibn_* and osnet_ain_*:
         appearance/osnet.py VARIANTS), then MobileNetV2 (appearance/mobilenetv2.py VARIANTS),
-        then MLFN (appearance/mlfn.py VARIANTS)."""
-        from . import mlfn, mobilenetv2, osnet
+        then MLFN (appearance/mlfn.py VARIANTS), then CLIP-ReID (appearance/clip.py VARIANTS, by
+        the file's name alone)."""
+        from . import clip, mlfn, mobilenetv2, osnet
         for family, cls in ((osnet, osnet.OSNetReID), (mobilenetv2, mobilenetv2.MobileNetV2ReID),
-                            (mlfn, mlfn.MLFNReID)):
+                            (mlfn, mlfn.MLFNReID), (clip, clip.ClipReID)):
             name = family.model_name(weights)
             if name is not None:
                 break
@@ -118,8 +120,8 @@ class ReIDDetectMultiBackend:
             raise NotImplementedError(
                 f"ReID weights {str(weights)!r}: only the OSNet family (osnet_x0_25 .. osnet_x1_0, "
                 "osnet_ibn_x1_0, osnet_ain_x1_0 and their other widths), MobileNetV2 "
-                "(mobilenetv2_x1_0, mobilenetv2_x1_4) and MLFN (mlfn) are rebuilt on the MI355X "
-                "path; pass "
+                "(mobilenetv2_x1_0, mobilenetv2_x1_4), MLFN (mlfn) and the CLIP-ReID ViT-B/16 "
+                "(clip) are rebuilt on the MI355X path; pass "
                 "model=<torch module> for other networks")
         w = Path(weights)
         if w.is_file():
