@@ -26,12 +26,9 @@ sys.path.insert(0, REPO)
 
 def main():
     ap = argparse.ArgumentParser()
-    from yolo_tracking_amd.appearance.clip import VARIANTS as CLIP
-    from yolo_tracking_amd.appearance.mlfn import VARIANTS as MLFN
-    from yolo_tracking_amd.appearance.mobilenetv2 import VARIANTS as MBV2
-    from yolo_tracking_amd.appearance.osnet import VARIANTS
+    from yolo_tracking_amd.appearance.reid_multibackend import FAMILIES
     ap.add_argument("--variant", default="osnet_x0_25",
-                    choices=sorted(VARIANTS) + sorted(MBV2) + sorted(MLFN) + sorted(CLIP),
+                    choices=[v for family, _ in FAMILIES for v in sorted(family.VARIANTS)],
                     help="OSNet variant (plain, osnet_ibn_* or osnet_ain_*; default osnet_x0_25) "
                          "or mobilenetv2_x1_0 / mobilenetv2_x1_4, or mlfn, or clip")
     ap.add_argument("--crops", type=int, default=1024)
@@ -40,42 +37,38 @@ def main():
     import torch
     from yolo_tracking_amd.appearance import ReIDDetectMultiBackend
     from yolo_tracking_amd.appearance.clip import CHUNK as CLIP_CHUNK
-    from yolo_tracking_amd.appearance.clip import ClipReID
-    from yolo_tracking_amd.appearance.mlfn import MLFNReID
-    from yolo_tracking_amd.appearance.mobilenetv2 import MobileNetV2ReID
-    from yolo_tracking_amd.appearance.osnet import OSNetReID
+    family, cls = next(f for f in FAMILIES if args.variant in f[0].VARIANTS)
+    kind = family.__name__.rsplit(".", 1)[1]   # osnet, mobilenetv2, mlfn or clip
     rng = np.random.default_rng(0)
     H, W, n = 1080, 1920, args.crops
     img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
     wh = rng.uniform(48, 192, (n, 2))
     xy = rng.uniform(0, 1, (n, 2)) * [W - 200, H - 200]
     boxes = np.concatenate([xy, xy + wh], 1)
-    mbv2, mlfn, clip = args.variant in MBV2, args.variant in MLFN, args.variant in CLIP
-    if clip:   # the HIP forward and the folded graph on PyTorch's kernels, its own chunk
+    # per family: the metric's label and one (half, chunk, hip, channels_last, fused) per run
+    if kind == "clip":   # the HIP forward and the folded graph on PyTorch's kernels, its own chunk
+        label = "CLIP-ReID"
         configs = [(half, CLIP_CHUNK, hip, False, None) for half in (False, True)
                    for hip in (True, False)]
-    elif mlfn:   # the HIP forward and the folded graph on PyTorch's kernels, NCHW
+    elif kind == "mlfn":   # the HIP forward and the folded graph on PyTorch's kernels, NCHW
+        label = "MLFN"
         configs = [(half, 1024, hip, False, None) for half in (False, True) for hip in (True, False)]
-    elif mbv2:   # (half, chunk, hip, channels_last, fused)
+    elif kind == "mobilenetv2":
+        label = "MobileNetV2"
         configs = [(half, 1024, hip, cl, fused) for half in (False, True)
                    for hip, cl, fused in ((True, False, True), (True, False, False),
                                           (False, True, None), (False, False, None))]
     else:
+        label = "OSNet"
         configs = [c + (None,) for c in (
             (False, 1024, True, False), (True, 1024, True, False), (False, 256, True, False),
             (True, 256, True, False), (False, 1024, False, True), (True, 1024, False, True),
             (True, 1024, False, False))]
     for half, chunk, hip, cl, fused in configs:
-        if clip:
-            net = ClipReID(args.variant, None, device="cuda:0", half=half, chunk=chunk, hip=hip)
-        elif mlfn:
-            net = MLFNReID(args.variant, None, device="cuda:0", half=half, chunk=chunk, hip=hip)
-        elif mbv2:
-            net = MobileNetV2ReID(args.variant, None, device="cuda:0", half=half, chunk=chunk,
-                                  channels_last=cl, hip=hip, fused=bool(fused))
-        else:
-            net = OSNetReID(args.variant, None, device="cuda:0", half=half, chunk=chunk,
-                            channels_last=cl, hip=hip)
+        extra = {"channels_last": cl} if kind in ("osnet", "mobilenetv2") else {}
+        if kind == "mobilenetv2":
+            extra["fused"] = bool(fused)
+        net = cls(args.variant, None, device="cuda:0", half=half, chunk=chunk, hip=hip, **extra)
         reid = ReIDDetectMultiBackend(None, device=0, fp16=half, model=net)
         crops = reid.preprocess(boxes, img)
         if half:
@@ -96,8 +89,7 @@ def main():
         for _ in range(args.steps):
             reid.get_features(boxes, img)
         e2e_ms = 1000 * (time.perf_counter() - t0) / args.steps
-        print(json.dumps({"metric": ("CLIP-ReID" if clip else "MLFN" if mlfn else "MobileNetV2" if mbv2 else "OSNet") +
-                          " ReID crops/s",
+        print(json.dumps({"metric": label + " ReID crops/s",
                           "variant": args.variant, "fused": fused,
                           "dtype": "f16" if half else "f32", "crops": n, "chunk": chunk,
                           "layout": "nhwc" if cl else "nchw", "hip_blocks": hip,

@@ -31,7 +31,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .osnet import BN_EPS
+from ._backbone import ReIDBackbone, bn_affine
 
 # name -> (width, layers, output_dim): ViT-B/16 (make_model.py:42-44)
 VARIANTS = {"clip": (768, 12, 512)}
@@ -131,42 +131,19 @@ def _tensor(torch, v):
     return v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
 
 
-class _Kernels:
-    """The HIP entry points on row-major matrices of one device and storage type.  Operands are
-    addresses (a tensor's data_ptr() plus a byte offset) with row strides in elements."""
+# csrc/clip.hip's entry points on row-major matrices, through the shared Kernels `K`.  Operands
+# are addresses (a tensor's data_ptr() plus a byte offset) with row strides in elements.
+def _linear(K, x, xs, m, k, w, ws, bias, nout, y, ys, act=0, res=None, rs=0):
+    K.call("yta_clip_linear", x, xs, w, ws, bias, res, rs, m, k, nout, act, K.half, y, ys)
 
-    def __init__(self, torch, device, dtype):
-        import ctypes
-        from .. import _lib
-        self.torch, self.device, self.dtype = torch, device, dtype
-        self.ct, self._lib = ctypes, _lib
-        self.half = int(dtype == torch.float16)
-        self.es = 2 if self.half else 4
-        self.P = ctypes.c_void_p
 
-    def lib(self):
-        return self._lib.load_library()
+def _layernorm(K, x, xs, m, c, gamma, beta, y, ys):
+    K.call("yta_clip_layernorm", x, xs, m, c, gamma.data_ptr(), beta.data_ptr(), LN_EPS, K.half, y,
+           ys)
 
-    def stream(self):
-        return self.ct.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
-    def empty(self, *shape):
-        return self.torch.empty(shape, dtype=self.dtype, device=self.device)
-
-    def linear(self, x, xs, m, k, w, ws, bias, nout, y, ys, act=0, res=None, rs=0):
-        self._lib.check(self.lib().yta_clip_linear(
-            self.P(x), xs, self.P(w), ws, self.P(bias), self.P(res), rs, m, k, nout, act,
-            self.half, self.P(y), ys, self.stream()))
-
-    def layernorm(self, x, xs, m, c, gamma, beta, y, ys):
-        self._lib.check(self.lib().yta_clip_layernorm(
-            self.P(x), xs, m, c, self.P(gamma.data_ptr()), self.P(beta.data_ptr()), LN_EPS,
-            self.half, self.P(y), ys, self.stream()))
-
-    def attention(self, qkv, n, L, width, lq, y):
-        self._lib.check(self.lib().yta_clip_attention(
-            self.P(qkv.data_ptr()), n, L, width, HEAD_DIM, lq, self.half, self.P(y.data_ptr()),
-            self.stream()))
+def _attention_hip(K, qkv, n, L, width, lq, y):
+    K.call("yta_clip_attention", qkv.data_ptr(), n, L, width, HEAD_DIM, lq, K.half, y.data_ptr())
 
 
 class _BlockParams:
@@ -242,7 +219,7 @@ def _block_hip(K, b, x, n, L, w, last=False):
     H, es = b.H, K.es
     m = n * L
     h = K.empty(m, w)
-    K.layernorm(x.data_ptr(), w, m, w, H["ln_1.weight"], H["ln_1.bias"], h.data_ptr(), w)
+    _layernorm(K, x.data_ptr(), w, m, w, H["ln_1.weight"], H["ln_1.bias"], h.data_ptr(), w)
     qkv = K.empty(n, L, 3 * w)
     wi, bi = H["attn.in_proj_weight"].data_ptr(), H["attn.in_proj_bias"].data_ptr()
     wo, bo = H["attn.out_proj.weight"].data_ptr(), H["attn.out_proj.bias"].data_ptr()
@@ -250,51 +227,40 @@ def _block_hip(K, b, x, n, L, w, last=False):
     wp, bp = H["mlp.c_proj.weight"].data_ptr(), H["mlp.c_proj.bias"].data_ptr()
     if last:
         # k | v of every token into their columns; q of token 0 of each sample into its row
-        K.linear(h.data_ptr(), w, m, w, wi + es * w * w, w, bi + 4 * w, 2 * w,
-                 qkv.data_ptr() + es * w, 3 * w)
-        K.linear(h.data_ptr(), L * w, n, w, wi, w, bi, w, qkv.data_ptr(), L * 3 * w)
+        _linear(K, h.data_ptr(), w, m, w, wi + es * w * w, w, bi + 4 * w, 2 * w,
+                qkv.data_ptr() + es * w, 3 * w)
+        _linear(K, h.data_ptr(), L * w, n, w, wi, w, bi, w, qkv.data_ptr(), L * 3 * w)
         rows, lq, xs = n, 1, L * w
         y = K.empty(n, w)
     else:
-        K.linear(h.data_ptr(), w, m, w, wi, w, bi, 3 * w, qkv.data_ptr(), 3 * w)
+        _linear(K, h.data_ptr(), w, m, w, wi, w, bi, 3 * w, qkv.data_ptr(), 3 * w)
         rows, lq, xs = m, L, w
         y = x
     a = K.empty(rows, w)
-    K.attention(qkv, n, L, w, lq, a)
-    K.linear(a.data_ptr(), w, rows, w, wo, w, bo, w, y.data_ptr(), w, res=x.data_ptr(), rs=xs)
+    _attention_hip(K, qkv, n, L, w, lq, a)
+    _linear(K, a.data_ptr(), w, rows, w, wo, w, bo, w, y.data_ptr(), w, res=x.data_ptr(), rs=xs)
     h = h if not last else K.empty(rows, w)
-    K.layernorm(y.data_ptr(), w, rows, w, H["ln_2.weight"], H["ln_2.bias"], h.data_ptr(), w)
+    _layernorm(K, y.data_ptr(), w, rows, w, H["ln_2.weight"], H["ln_2.bias"], h.data_ptr(), w)
     hid = K.empty(rows, 4 * w)
-    K.linear(h.data_ptr(), w, rows, w, wf, w, bf, 4 * w, hid.data_ptr(), 4 * w, act=1)
-    K.linear(hid.data_ptr(), 4 * w, rows, 4 * w, wp, 4 * w, bp, w, y.data_ptr(), w,
-             res=y.data_ptr(), rs=w)
+    _linear(K, h.data_ptr(), w, rows, w, wf, w, bf, 4 * w, hid.data_ptr(), 4 * w, act=1)
+    _linear(K, hid.data_ptr(), 4 * w, rows, 4 * w, wp, 4 * w, bp, w, y.data_ptr(), w,
+            res=y.data_ptr(), rs=w)
     return y
 
 
-def _dtype(torch, half, double, hip):
-    if double and (half or hip):
-        raise ValueError("double=True is the float64 evaluation of the hip=False graph")
-    return torch.float64 if double else torch.float16 if half else torch.float32
-
-
-class ClipBlock:
+class ClipBlock(ReIDBackbone):
     """One ResidualAttentionBlock (model.py:169-190) from a state_dict in the module's keys:
     x (N, L, width) -> (N, L, width).  (The reference module takes (L, N, width).)  ClipReID is
     twelve of these between the token kernel and the neck; the block fixture runs one alone."""
 
     def __init__(self, state_dict, width, device="cuda:0", half=False, hip=True, double=False):
-        import torch
-        self.torch = torch
-        self.device = torch.device(device)
-        self.hip = bool(hip) and self.device.type == "cuda"
-        self.dtype = _dtype(torch, half, double, self.hip)
+        self._setup(device, half, hip, double=double)
+        torch = self.torch
         self.width = int(width)
         if self.width % HEAD_DIM:
             raise ValueError(f"width {self.width} is not a multiple of the head dimension 64")
         self.params = _BlockParams(torch, state_dict, "", self.width, self.device, self.dtype,
                                    self.hip)
-        if self.hip:
-            self.K = _Kernels(torch, self.device, self.dtype)
 
     def __call__(self, x):
         torch = self.torch
@@ -306,7 +272,7 @@ class ClipBlock:
             return _block_hip(self.K, self.params, x.clone(), n, L, w)
 
 
-class ClipReID:
+class ClipReID(ReIDBackbone):
     """Eval-mode CLIP-ReID feature extractor: crops (N, 3, H, W) -> (N, width + output_dim) in the
     crops' dtype (float32 or float16), on the crops' device.  Width, output_dim, the token count
     and the layer count come from the state_dict; `name` stands for the sizes of the freshly
@@ -314,15 +280,10 @@ class ClipReID:
 
     def __init__(self, name="clip", state_dict=None, device="cuda:0", half=False, chunk=CHUNK,
                  hip=True, double=False):
-        import torch
         if name not in VARIANTS:
             raise KeyError(f"unknown CLIP-ReID variant {name!r}")
-        self.torch = torch
+        self._setup(device, half, hip, chunk, double=double)
         self.name = name
-        self.chunk = int(chunk)
-        self.device = torch.device(device)
-        self.hip = bool(hip) and self.device.type == "cuda"
-        self.dtype = _dtype(torch, half, double, self.hip)
         if state_dict is None:
             w0, l0, o0 = VARIANTS[name]
             state_dict = random_state_dict(0, w0, 128, o0, l0)
@@ -375,8 +336,8 @@ class ClipReID:
         # the necks, folded in float64: bottleneck into a second affine of ln_post,
         # bottleneck_proj into proj's columns and a bias
         def neck(key, c):
-            s = f64(key + ".weight", (c,)) / (f64(key + ".running_var", (c,)) + BN_EPS).sqrt()
-            return s, f64(key + ".bias", (c,)) - f64(key + ".running_mean", (c,)) * s
+            return bn_affine({f"{key}.{p}": f64(f"{key}.{p}", (c,)) for p in
+                              ("weight", "running_var", "bias", "running_mean")}, key)
         g, b = f64("ln_post.weight", (width,)), f64("ln_post.bias", (width,))
         s1, t1 = neck("bottleneck", width)
         s2, t2 = neck("bottleneck_proj", self.output_dim)
@@ -391,8 +352,6 @@ class ClipReID:
         self.W = {k: v.to(self.device, self.dtype).contiguous() for k, v in big.items()}
         self.blocks = [_BlockParams(torch, sd, f"transformer.resblocks.{i}.", width, self.device,
                                     self.dtype, self.hip) for i in range(layers)]
-        if self.hip:
-            self.K = _Kernels(torch, self.device, self.dtype)
 
     def _grid(self, crops):
         n, c, h, w = crops.shape
@@ -428,37 +387,22 @@ class ClipReID:
     def _forward_hip(self, crops):
         K, S, W = self.K, self.S, self.W
         n, g = self._grid(crops)
-        w, L, od, P = self.width, self.tokens, self.output_dim, K.P
+        w, L, od = self.width, self.tokens, self.output_dim
         x = crops.to(self.device, self.dtype).contiguous()
         pat = K.empty(n * g, 3 * PATCH * PATCH)
-        K._lib.check(K.lib().yta_clip_patches(P(x.data_ptr()), n, x.shape[2], x.shape[3], K.half,
-                                              P(pat.data_ptr()), K.stream()))
+        K.call("yta_clip_patches", x.data_ptr(), n, x.shape[2], x.shape[3], K.half, pat.data_ptr())
         emb = K.empty(n * g, w)
-        K.linear(pat.data_ptr(), 768, n * g, 768, W["conv1"].data_ptr(), 768, None, w,
-                 emb.data_ptr(), w)
+        _linear(K, pat.data_ptr(), 768, n * g, 768, W["conv1"].data_ptr(), 768, None, w,
+                emb.data_ptr(), w)
         x = K.empty(n, L, w)
-        K._lib.check(K.lib().yta_clip_tokens(
-            P(emb.data_ptr()), w, P(S["cls"].data_ptr()), P(S["pos"].data_ptr()), n, g, w,
-            P(S["pre_g"].data_ptr()), P(S["pre_b"].data_ptr()), LN_EPS, K.half, P(x.data_ptr()),
-            K.stream()))
+        K.call("yta_clip_tokens", emb.data_ptr(), w, S["cls"].data_ptr(), S["pos"].data_ptr(), n, g,
+               w, S["pre_g"].data_ptr(), S["pre_b"].data_ptr(), LN_EPS, K.half, x.data_ptr())
         for i, b in enumerate(self.blocks):
             x = _block_hip(K, b, x, n, L, w, i == self.layers - 1)
         out = K.empty(n, w + od)
-        K.layernorm(x.data_ptr(), w, n, w, S["neck_g"], S["neck_b"], out.data_ptr(), w + od)
+        _layernorm(K, x.data_ptr(), w, n, w, S["neck_g"], S["neck_b"], out.data_ptr(), w + od)
         c = K.empty(n, w)
-        K.layernorm(x.data_ptr(), w, n, w, S["post_g"], S["post_b"], c.data_ptr(), w)
-        K.linear(c.data_ptr(), w, n, w, W["proj"].data_ptr(), w, S["proj_b"].data_ptr(), od,
-                 out.data_ptr() + K.es * w, w + od)
+        _layernorm(K, x.data_ptr(), w, n, w, S["post_g"], S["post_b"], c.data_ptr(), w)
+        _linear(K, c.data_ptr(), w, n, w, W["proj"].data_ptr(), w, S["proj_b"].data_ptr(), od,
+                out.data_ptr() + K.es * w, w + od)
         return out
-
-    def _forward(self, crops):
-        return self._forward_hip(crops) if self.hip else self._forward_torch(crops)
-
-    def __call__(self, crops):
-        torch = self.torch
-        with torch.no_grad():
-            n = crops.shape[0]
-            if n <= self.chunk:
-                return self._forward(crops)
-            return torch.cat([self._forward(crops[i:i + self.chunk])
-                              for i in range(0, n, self.chunk)])

@@ -26,7 +26,7 @@ import math
 
 import numpy as np
 
-from .osnet import BN_EPS, CHUNK
+from ._backbone import CHUNK, ReIDBackbone, f32, fold_bn, kmajor, to_f64
 
 # name -> (groups, channels, embed_dim): mlfn.py MLFN.__init__'s defaults
 VARIANTS = {"mlfn": (32, (64, 256, 512, 1024, 2048), 1024)}
@@ -139,109 +139,48 @@ def random_state_dict(seed=0, groups=32, channels=(64, 256, 512, 1024, 2048), em
     return sd
 
 
-def _fold(sd, conv, bn):
-    """(weight, bias) of conv followed by its eval-mode BatchNorm, in the tensors' float64."""
-    w = sd[conv + ".weight"]
-    scale = sd[bn + ".weight"] / (sd[bn + ".running_var"] + BN_EPS).sqrt()
-    bias = sd[bn + ".bias"] - sd[bn + ".running_mean"] * scale
-    if conv + ".bias" in sd:
-        bias = bias + sd[conv + ".bias"] * scale
-    return w * scale.reshape(-1, 1, 1, 1), bias
+def _subsample(K, x, s):
+    n, c, h, w = x.shape
+    y = K.empty(n, c, (h - 1) // s + 1, (w - 1) // s + 1)
+    K.call("yta_mlfn_subsample", x.data_ptr(), n, c, h, w, s, K.half, y.data_ptr())
+    return y
 
 
-def _f64(sd, torch):
-    return {k: torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).to(torch.float64)
-            for k, v in sd.items() if not k.startswith("classifier.")}
+def _gconv(K, x, w, b, groups, stride, scale_ptr, scale_stride):
+    n, c, h, wd = x.shape
+    y = K.empty(n, c, (h - 1) // stride + 1, (wd - 1) // stride + 1)
+    K.call("yta_mlfn_gconv3x3", x.data_ptr(), w.data_ptr(), b.data_ptr(), scale_ptr, scale_stride,
+           n, c, groups, h, wd, stride, K.half, y.data_ptr())
+    return y
 
 
-class _Kernels:
-    """The HIP entry points on NCHW-contiguous tensors of one device and storage type."""
-
-    def __init__(self, torch, device, dtype):
-        import ctypes
-        from .. import _lib
-        self.torch, self.device, self.dtype = torch, device, dtype
-        self.ct, self._lib = ctypes, _lib
-        self.half = int(dtype == torch.float16)
-        self.P = ctypes.c_void_p
-
-    def lib(self):
-        return self._lib.load_library()
-
-    def stream(self):
-        return self.ct.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
-    def empty(self, *shape, dtype=None):
-        return self.torch.empty(shape, dtype=dtype or self.dtype, device=self.device)
-
-    def pw(self, x, w, bias, *, k, cout, P, N, relu, res=None, rows=False):
-        """1x1 convolution through yta_osnet_pointwise: x (N, k, P) -> (N, cout, P); rows=True:
-        x (P, k) -> (P, cout), the samples on the pixel axis (a linear layer as one GEMM)."""
-        out = self.empty(P, cout) if rows else self.empty(N, cout, P)
-        a = self._lib.PwArgs()
-        a.x1, a.w, a.bias, a.y = x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr()
-        if rows:
-            a.x1n, a.x1c, a.x1p = 0, 1, k
-            a.yn, a.yc, a.yp = 0, 1, cout
-        else:
-            a.x1n, a.x1c, a.x1p = k * P, P, 1
-            a.yn, a.yc, a.yp = cout * P, P, 1
-        if res is not None:
-            a.res = res.data_ptr()
-            a.rn, a.rc, a.rp = a.yn, a.yc, a.yp
-        a.k1, a.k2, a.G, a.cout_g, a.P, a.N, a.relu = k, 0, 1, cout, P, N, int(relu)
-        self._lib.check(self.lib().yta_osnet_pointwise(self.ct.byref(a), self.half, self.stream()))
-        return out
-
-    def pool(self, x, kind):
-        n, c, h, w = x.shape
-        y = self.empty(n, c) if kind == 2 else self.empty(n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
-        self._lib.check(self.lib().yta_osnet_pool(self.P(x.data_ptr()), n, c, h, w, kind, self.half,
-                                                  self.P(y.data_ptr()), self.stream()))
-        return y
-
-    def subsample(self, x, s):
-        n, c, h, w = x.shape
-        y = self.empty(n, c, (h - 1) // s + 1, (w - 1) // s + 1)
-        self._lib.check(self.lib().yta_mlfn_subsample(self.P(x.data_ptr()), n, c, h, w, s, self.half,
-                                                      self.P(y.data_ptr()), self.stream()))
-        return y
-
-    def gconv(self, x, w, b, groups, stride, scale_ptr, scale_stride):
-        n, c, h, wd = x.shape
-        y = self.empty(n, c, (h - 1) // stride + 1, (wd - 1) // stride + 1)
-        self._lib.check(self.lib().yta_mlfn_gconv3x3(
-            self.P(x.data_ptr()), self.P(w.data_ptr()), self.P(b.data_ptr()), self.P(scale_ptr),
-            scale_stride, n, c, groups, h, wd, stride, self.half, self.P(y.data_ptr()),
-            self.stream()))
-        return y
+def _linear(K, x, w, b, k, cout, n):
+    """relu(x w^T + b) on rows x (n, k) as one GEMM, the samples on the pixel axis."""
+    return K.pw(x, w, b, k1=k, cout_g=cout, P=n, N=1, relu=1, x1s=(0, 1, k), ys=(0, 1, cout),
+                out=K.empty(n, cout))
 
 
-class MLFNBlockGraph:
+class MLFNBlockGraph(ReIDBackbone):
     """One eval-mode MLFNBlock (mlfn.py:18-92) with folded BatchNorms from a state_dict whose keys
     start with `prefix`: x (N, cin, H, W) -> (y (N, cout, Ho, Wo), s (N, groups)).  MLFNReID is 16
     of these between the stem and the two projections; the block fixtures run one alone."""
 
     def __init__(self, state_dict, cin, cout, stride, fsm_channels, groups=32, prefix="",
                  device="cuda:0", half=False, hip=True, _folded=None):
-        import torch
-        self.torch = torch
-        self.device = torch.device(device)
-        self.hip = bool(hip) and self.device.type == "cuda"
-        self.dtype = torch.float16 if half else torch.float32
+        self._setup(device, half, hip)
         self.cin, self.cout, self.mid, self.stride = cin, cout, cout // 2, stride
         self.f0, self.f1 = fsm_channels
         self.groups = groups
         self.down = cin != cout or stride > 1
         if self.mid % groups:
             raise ValueError(f"groups {groups} does not divide the {self.mid} mid channels")
-        sd = _f64(state_dict, torch) if _folded is None else _folded
+        sd = to_f64(state_dict, drop=("classifier.",)) if _folded is None else _folded
         p = prefix
         names = [("fm_conv1", "fm_bn1"), ("fm_conv2", "fm_bn2"), ("fm_conv3", "fm_bn3"),
                  ("fsm.1", "fsm.2"), ("fsm.4", "fsm.5"), ("fsm.7", "fsm.8")]
         if self.down:
             names.append(("downsample.0", "downsample.1"))
-        folded = [_fold(sd, p + c, p + b) for c, b in names]
+        folded = [fold_bn(sd, p + c, p + b) for c, b in names]
         shapes = [(self.mid, cin, 1, 1), (self.mid, self.mid // groups, 3, 3),
                   (cout, self.mid, 1, 1), (self.f0, cin, 1, 1), (self.f1, self.f0, 1, 1),
                   (groups, self.f1, 1, 1), (cout, cin, 1, 1)]
@@ -249,16 +188,13 @@ class MLFNBlockGraph:
             if tuple(w.shape) != shape:
                 raise ValueError(f"{p + c}.weight is {tuple(w.shape)}, expected {shape}")
         # the torch graph's parameters (storage type) and the kernels' (float32; 1x1s k-major)
-        self.T = [(w.to(self.device, self.dtype).contiguous(),
-                   b.to(self.device, self.dtype).contiguous()) for w, b in folded]
+        d = self.device
+        self.T = [(w.to(d, self.dtype).contiguous(), b.to(d, self.dtype).contiguous())
+                  for w, b in folded]
         self.H = None
         if self.hip:
-            def f32(v):
-                return v.to(self.device, torch.float32).contiguous()
-            self.H = [(f32(w.reshape(self.mid, -1)) if i == 1 else
-                       f32(w.reshape(w.shape[0], w.shape[1]).t()), f32(b))
+            self.H = [(f32(w.reshape(self.mid, -1), d) if i == 1 else kmajor(w, d), f32(b, d))
                       for i, (w, b) in enumerate(folded)]
-            self.K = _Kernels(torch, self.device, self.dtype)
 
     def forward_torch(self, x):
         F = self.torch.nn.functional
@@ -284,21 +220,18 @@ class MLFNBlockGraph:
         sel_ptr = sel.data_ptr() + 4 * slot * G
         selt_ptr = None if sel_t is None else sel_t.data_ptr() + sel_t.element_size() * slot * G
         pooled = K.pool(x, 2)
-        P = K.P
-        K._lib.check(K.lib().yta_mlfn_fsm(
-            P(pooled.data_ptr()), n, self.cin, self.f0, self.f1, G, P(H[3][0].data_ptr()),
-            P(H[3][1].data_ptr()), P(H[4][0].data_ptr()), P(H[4][1].data_ptr()),
-            P(H[5][0].data_ptr()), P(H[5][1].data_ptr()), K.half, P(sel_ptr), row, P(selt_ptr),
-            row, K.stream()))
-        m = K.pw(x, *H[0], k=self.cin, cout=self.mid, P=h * w, N=n, relu=1).view(n, self.mid, h, w)
-        m = K.gconv(m, *H[1], G, self.stride, sel_ptr, row)
+        K.call("yta_mlfn_fsm", pooled.data_ptr(), n, self.cin, self.f0, self.f1, G,
+               *[t.data_ptr() for t in (*H[3], *H[4], *H[5])], K.half, sel_ptr, row, selt_ptr, row)
+        m = K.pw(x, *H[0], k1=self.cin, cout_g=self.mid, P=h * w, N=n, relu=1) \
+            .view(n, self.mid, h, w)
+        m = _gconv(K, m, *H[1], G, self.stride, sel_ptr, row)
         ho, wo = m.shape[2:]
         if self.down:
-            m = K.pw(m, *H[2], k=self.mid, cout=self.cout, P=ho * wo, N=n, relu=1)
-            xs = K.subsample(x, self.stride) if self.stride > 1 else x
-            y = K.pw(xs, *H[6], k=self.cin, cout=self.cout, P=ho * wo, N=n, relu=1, res=m)
+            m = K.pw(m, *H[2], k1=self.mid, cout_g=self.cout, P=ho * wo, N=n, relu=1)
+            xs = _subsample(K, x, self.stride) if self.stride > 1 else x
+            y = K.pw(xs, *H[6], k1=self.cin, cout_g=self.cout, P=ho * wo, N=n, relu=1, res=m)
         else:
-            y = K.pw(m, *H[2], k=self.mid, cout=self.cout, P=ho * wo, N=n, relu=3, res=x)
+            y = K.pw(m, *H[2], k1=self.mid, cout_g=self.cout, P=ho * wo, N=n, relu=3, res=x)
         return y.view(n, self.cout, ho, wo)
 
     def __call__(self, x):
@@ -312,18 +245,16 @@ class MLFNBlockGraph:
             return y, sel.to(self.dtype)
 
 
-class MLFNReID:
+class MLFNReID(ReIDBackbone):
     """Eval-mode MLFN feature extractor: crops (N, 3, H, W) -> (N, embed_dim) in the crops' dtype
     (float32 or float16), on the crops' device.  groups / channels / embed_dim override the sizes
     the name stands for (the golden network is groups 4, channels 16 .. 256, 64 features)."""
 
     def __init__(self, name="mlfn", state_dict=None, device="cuda:0", half=False, chunk=CHUNK,
                  hip=True, groups=None, channels=None, embed_dim=None):
-        import torch
         if name not in VARIANTS:
             raise KeyError(f"unknown MLFN variant {name!r}")
         g0, c0, e0 = VARIANTS[name]
-        self.torch = torch
         self.name = name
         self.groups = g0 if groups is None else int(groups)
         self.channels = tuple(c0 if channels is None else channels)
@@ -332,62 +263,47 @@ class MLFNReID:
         if self.channels[0] % 16:
             raise ValueError(f"channels[0] = {self.channels[0]}: the stem kernel takes a multiple "
                              "of 16 output channels")
-        self.chunk = int(chunk)
-        self.device = torch.device(device)
-        self.hip = bool(hip) and self.device.type == "cuda"
-        self.dtype = torch.float16 if half else torch.float32
+        self._setup(device, half, hip, chunk)
         sd = random_state_dict(0, self.groups, self.channels, self.embed_dim) \
             if state_dict is None else state_dict
-        self._build(_f64(sd, torch))
+        self._build(to_f64(sd, drop=("classifier.",)))
 
     def _build(self, sd):
-        torch, c = self.torch, self.channels
-        ws, bs = _fold(sd, "conv1", "bn1")
-        wx, bx = _fold(sd, "fc_x.0", "fc_x.1")
-        wsel, bsel = _fold(sd, "fc_s.0", "fc_s.1")
+        c, d = self.channels, self.device
+        ws, bs = fold_bn(sd, "conv1", "bn1")
+        wx, bx = fold_bn(sd, "fc_x.0", "fc_x.1")
+        wsel, bsel = fold_bn(sd, "fc_s.0", "fc_s.1")
         want = ((c[0], 3, 7, 7), (self.embed_dim, c[4], 1, 1),
                 (self.embed_dim, self.groups * BLOCKS, 1, 1))
         got = tuple(tuple(w.shape) for w in (ws, wx, wsel))
         if got != want:
             raise ValueError(f"{self.name}: the state_dict's conv1 / fc_x.0 / fc_s.0 weights are "
                              f"{got}, expected {want}")
-        self.T = [(w.to(self.device, self.dtype).contiguous(),
-                   b.to(self.device, self.dtype).contiguous())
+        self.T = [(w.to(d, self.dtype).contiguous(), b.to(d, self.dtype).contiguous())
                   for w, b in ((ws, bs), (wx, bx), (wsel, bsel))]
         if self.hip:
-            def f32(v):
-                return v.to(self.device, torch.float32).contiguous()
-            self.H = [(f32(ws), f32(bs))] + [(f32(w.reshape(w.shape[0], w.shape[1]).t()), f32(b))
-                                             for w, b in ((wx, bx), (wsel, bsel))]
-            self.K = _Kernels(torch, self.device, self.dtype)
+            self.H = [(f32(ws, d), f32(bs, d)), (kmajor(wx, d), f32(bx, d)),
+                      (kmajor(wsel, d), f32(bsel, d))]
         self.blocks = [MLFNBlockGraph(None, cin, cout, stride, fsm, self.groups,
-                                      prefix=f"feature.{i}.", device=self.device,
-                                      half=self.dtype == torch.float16, hip=self.hip, _folded=sd)
+                                      prefix=f"feature.{i}.", device=d,
+                                      half=self.dtype == self.torch.float16, hip=self.hip,
+                                      _folded=sd)
                        for i, (cin, cout, stride, fsm) in enumerate(self.layout)]
 
     def _forward_hip(self, crops):
         torch, K = self.torch, self.K
         x = crops.to(self.device, self.dtype).contiguous()
-        n, _, h, w = x.shape
-        c0, G = self.channels[0], self.groups
-        ws, bs = self.H[0]
-        y = K.empty(n, c0, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
-        K._lib.check(K.lib().yta_osnet_stem(K.P(x.data_ptr()), n, h, w, K.P(ws.data_ptr()),
-                                            K.P(bs.data_ptr()), c0, K.half, K.P(y.data_ptr()),
-                                            K.stream()))
-        x = K.pool(y, 0)
+        n, G = x.shape[0], self.groups
+        x = K.pool(K.stem(x, *self.H[0]), 0)
         sel = K.empty(n, BLOCKS * G, dtype=torch.float32)
         sel_t = K.empty(n, BLOCKS * G) if K.half else None
         for i, blk in enumerate(self.blocks):
             x = blk.forward_hip(x, sel, sel_t, i)
         pooled = K.pool(x, 2)
-        fx = K.pw(pooled, *self.H[1], k=self.channels[4], cout=self.embed_dim, P=n, N=1, relu=1,
-                  rows=True)
-        fs = K.pw(sel_t if K.half else sel, *self.H[2], k=BLOCKS * G, cout=self.embed_dim, P=n,
-                  N=1, relu=1, rows=True)
+        fx = _linear(K, pooled, *self.H[1], self.channels[4], self.embed_dim, n)
+        fs = _linear(K, sel_t if K.half else sel, *self.H[2], BLOCKS * G, self.embed_dim, n)
         v = K.empty(n, self.embed_dim)
-        K._lib.check(K.lib().yta_mlfn_mean2(K.P(fx.data_ptr()), K.P(fs.data_ptr()), v.numel(),
-                                            K.half, K.P(v.data_ptr()), K.stream()))
+        K.call("yta_mlfn_mean2", fx.data_ptr(), fs.data_ptr(), v.numel(), K.half, v.data_ptr())
         return v
 
     def _forward_torch(self, crops):
@@ -404,15 +320,3 @@ class MLFNReID:
         fx = F.relu(F.conv2d(x, *self.T[1]))
         fs = F.relu(F.conv2d(torch.cat(sel, 1)[:, :, None, None], *self.T[2]))
         return ((fx + fs) * 0.5).flatten(1)
-
-    def _forward(self, crops):
-        return self._forward_hip(crops) if self.hip else self._forward_torch(crops)
-
-    def __call__(self, crops):
-        torch = self.torch
-        with torch.no_grad():
-            n = crops.shape[0]
-            if n <= self.chunk:
-                return self._forward(crops)
-            return torch.cat([self._forward(crops[i:i + self.chunk])
-                              for i in range(0, n, self.chunk)])

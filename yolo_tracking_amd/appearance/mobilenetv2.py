@@ -22,7 +22,7 @@ import math
 
 import numpy as np
 
-from .osnet import BN_EPS, CHUNK
+from ._backbone import CHUNK, ReIDBackbone, f32, fold_bn, kmajor, to_f64
 
 VARIANTS = {"mobilenetv2_x1_0": 1.0, "mobilenetv2_x1_4": 1.4}
 # MobileNetV2.__init__'s _make_layer calls: (expansion t, channels c at width 1, blocks n, stride s)
@@ -90,7 +90,7 @@ def random_state_dict(name="mobilenetv2_x1_0", seed=0, width_mult=None):
     return sd
 
 
-class MobileNetV2ReID:
+class MobileNetV2ReID(ReIDBackbone):
     """Eval-mode MobileNetV2 feature extractor: crops (N, 3, H, W) -> (N, feature_dim) in the
     crops' dtype (float32 or float16), on the crops' device.  width_mult overrides the width the
     name stands for (the golden network is x0.25).  count_clamped (hip=False only): after a
@@ -99,129 +99,77 @@ class MobileNetV2ReID:
     def __init__(self, name="mobilenetv2_x1_0", state_dict=None, device="cuda:0", half=False,
                  chunk=CHUNK, hip=True, fused=True, width_mult=None, channels_last=False,
                  count_clamped=False):
-        import torch
         if name not in VARIANTS:
             raise KeyError(f"unknown MobileNetV2 variant {name!r}")
-        self.torch = torch
+        self._setup(device, half, hip, chunk)
+        torch = self.torch
         self.name = name
         self.width_mult = VARIANTS[name] if width_mult is None else width_mult
         self.c0, self.layout, self.feature_dim = layout(self.width_mult)
-        self.chunk = int(chunk)
-        self.device = torch.device(device)
-        self.hip = bool(hip) and self.device.type == "cuda"
         self.fused = bool(fused)
         if self.hip and channels_last:
             raise ValueError("the HIP kernels take NCHW planes (channels_last=False)")
         self.fmt = torch.channels_last if channels_last else torch.contiguous_format
-        self.dtype = torch.float16 if half else torch.float32
         self.count_clamped = bool(count_clamped)
         self.clamped = None
         sd = random_state_dict(name, width_mult=width_mult) if state_dict is None else state_dict
-        self._build({k: torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v)
-                     .to(torch.float64) for k, v in sd.items() if not k.startswith("classifier.")})
+        self._build(to_f64(sd, drop=("classifier.",)))
 
     # ---- parameter folding (float64 on the host, then cast once)
-    @staticmethod
-    def _fold(sd, conv, bn):
-        w = sd[conv + ".weight"]
-        scale = sd[bn + ".weight"] / (sd[bn + ".running_var"] + BN_EPS).sqrt()
-        return w * scale.reshape(-1, 1, 1, 1), sd[bn + ".bias"] - sd[bn + ".running_mean"] * scale
-
     def _t(self, x):
         x = x.to(self.device, self.dtype)
         return x.contiguous(memory_format=self.fmt) if x.dim() == 4 and x.shape[1] > 1 \
             else x.contiguous()
 
-    def _f32(self, x):
-        return x.to(self.device, self.torch.float32).contiguous()
-
-    def _kmajor(self, w):
-        """A 1x1 weight (cout, cin, 1, 1) as the float32 [cin][cout] yta_osnet_pointwise and
-        yta_mbv2_expand_dw read (lanes along the output channels)."""
-        return self._f32(w.reshape(w.shape[0], w.shape[1]).t())
-
     def _build(self, sd):
-        ws, bs = self._fold(sd, "conv1.conv", "conv1.bn")
-        w9, b9 = self._fold(sd, "conv9.conv", "conv9.bn")
+        d = self.device
+        ws, bs = fold_bn(sd, "conv1.conv", "conv1.bn")
+        w9, b9 = fold_bn(sd, "conv9.conv", "conv9.bn")
         if ws.shape[0] != self.c0 or w9.shape[0] != self.feature_dim:
             raise ValueError(f"{self.name} (width {self.width_mult}): the state_dict has "
                              f"{ws.shape[0]} stem channels and {w9.shape[0]} features, expected "
                              f"{self.c0} and {self.feature_dim}")
         self.T = {"stem": (self._t(ws), self._t(bs)), "conv9": (self._t(w9), self._t(b9))}
-        self.H = {"stem": (self._f32(ws), self._f32(bs)), "conv9": (self._kmajor(w9), self._f32(b9))}
+        self.H = {"stem": (f32(ws, d), f32(bs, d)), "conv9": (kmajor(w9, d), f32(b9, d))}
         self.blocks = []
         for key, cin, cmid, cout, stride, res in self.layout:
-            w1, b1 = self._fold(sd, key + ".conv1.conv", key + ".conv1.bn")
-            wd, bd = self._fold(sd, key + ".dwconv2.conv", key + ".dwconv2.bn")
-            w3, b3 = self._fold(sd, key + ".conv3.0", key + ".conv3.1")
+            w1, b1 = fold_bn(sd, key + ".conv1.conv", key + ".conv1.bn")
+            wd, bd = fold_bn(sd, key + ".dwconv2.conv", key + ".dwconv2.bn")
+            w3, b3 = fold_bn(sd, key + ".conv3.0", key + ".conv3.1")
             assert w1.shape[:2] == (cmid, cin) and w3.shape[:2] == (cout, cmid), key
             tp = tuple(self._t(v) for v in (w1, b1, wd, bd, w3, b3))
-            hp = (self._kmajor(w1), self._f32(b1), self._f32(wd.reshape(cmid, 9)), self._f32(bd),
-                  self._kmajor(w3), self._f32(b3))
+            hp = (kmajor(w1, d), f32(b1, d), f32(wd.reshape(cmid, 9), d), f32(bd, d),
+                  kmajor(w3, d), f32(b3, d))
             self.blocks.append((cin, cmid, cout, stride, res, tp, hp))
 
     # ---- the HIP forward
-    def _pw(self, x, w, bias, *, k, cout, P, N, relu, res=None):
-        """1x1 convolution through yta_osnet_pointwise (NCHW-contiguous x, res and output)."""
-        from .. import _lib
-        out = self.torch.empty((N, cout, P), dtype=self.dtype, device=self.device)
-        a = _lib.PwArgs()
-        a.x1 = x.data_ptr()
-        a.x1n, a.x1c, a.x1p = k * P, P, 1
-        a.w = w.data_ptr()
-        a.bias = bias.data_ptr()
-        if res is not None:
-            a.res = res.data_ptr()
-            a.rn, a.rc, a.rp = cout * P, P, 1
-        a.y = out.data_ptr()
-        a.yn, a.yc, a.yp = cout * P, P, 1
-        a.k1, a.k2, a.G, a.cout_g, a.P, a.N, a.relu = k, 0, 1, cout, P, N, int(relu)
-        _lib.check(_lib.load_library().yta_osnet_pointwise(self._ctypes.byref(a), self._half,
-                                                           self._stream()))
-        return out
-
-    def _stream(self):
-        return self._ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
     def _forward_hip(self, crops):
-        import ctypes
-        from .. import _lib
-        torch = self.torch
-        self._ctypes = ctypes
-        self._half = int(self.dtype == torch.float16)
-        lib = _lib.load_library()
-        P = ctypes.c_void_p
+        K = self.K
         x = crops.to(self.device, self.dtype).contiguous()
         n, _, h, w = x.shape
         ws, bs = self.H["stem"]
         h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        y = torch.empty((n, self.c0, h, w), dtype=self.dtype, device=self.device)
-        _lib.check(lib.yta_mbv2_stem(P(x.data_ptr()), n, x.shape[2], x.shape[3], P(ws.data_ptr()),
-                                     P(bs.data_ptr()), self.c0, self._half, P(y.data_ptr()),
-                                     self._stream()))
+        y = K.empty(n, self.c0, h, w)
+        K.call("yta_mbv2_stem", x.data_ptr(), n, x.shape[2], x.shape[3], ws.data_ptr(),
+               bs.data_ptr(), self.c0, K.half, y.data_ptr())
         x = y
         for cin, cmid, cout, s, res, _, (w1, b1, wd, bd, w3, b3) in self.blocks:
+            pw1, pb1, pwd, pbd = w1.data_ptr(), b1.data_ptr(), wd.data_ptr(), bd.data_ptr()
             ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
-            m = torch.empty((n, cmid, ho, wo), dtype=self.dtype, device=self.device)
+            m = K.empty(n, cmid, ho, wo)
             if self.fused:
-                _lib.check(lib.yta_mbv2_expand_dw(
-                    P(x.data_ptr()), P(w1.data_ptr()), P(b1.data_ptr()), P(wd.data_ptr()),
-                    P(bd.data_ptr()), n, cin, cmid, h, w, s, self._half, P(m.data_ptr()),
-                    self._stream()))
+                K.call("yta_mbv2_expand_dw", x.data_ptr(), pw1, pb1, pwd, pbd, n, cin, cmid, h, w,
+                       s, K.half, m.data_ptr())
             else:
-                e = self._pw(x, w1, b1, k=cin, cout=cmid, P=h * w, N=n, relu=2)
-                _lib.check(lib.yta_mbv2_dw3x3(
-                    P(e.data_ptr()), P(wd.data_ptr()), P(bd.data_ptr()), n, cmid, h, w, s,
-                    self._half, P(m.data_ptr()), self._stream()))
-            x = self._pw(m, w3, b3, k=cmid, cout=cout, P=ho * wo, N=n, relu=0,
-                         res=x if res else None).view(n, cout, ho, wo)
+                e = K.pw(x, w1, b1, k1=cin, cout_g=cmid, P=h * w, N=n, relu=2)
+                K.call("yta_mbv2_dw3x3", e.data_ptr(), pwd, pbd, n, cmid, h, w, s, K.half,
+                       m.data_ptr())
+            x = K.pw(m, w3, b3, k1=cmid, cout_g=cout, P=ho * wo, N=n, relu=0,
+                     res=x if res else None).view(n, cout, ho, wo)
             h, w = ho, wo
         w9, b9 = self.H["conv9"]
-        y = self._pw(x, w9, b9, k=x.shape[1], cout=self.feature_dim, P=h * w, N=n, relu=2)
-        feat = torch.empty((n, self.feature_dim), dtype=self.dtype, device=self.device)
-        _lib.check(lib.yta_osnet_pool(P(y.data_ptr()), n, self.feature_dim, h, w, 2, self._half,
-                                      P(feat.data_ptr()), self._stream()))
-        return feat
+        y = K.pw(x, w9, b9, k1=x.shape[1], cout_g=self.feature_dim, P=h * w, N=n, relu=2)
+        return K.pool(y.view(n, self.feature_dim, h, w), 2)
 
     # ---- the same graph on PyTorch's operators
     def _relu6(self, x):
@@ -244,15 +192,3 @@ class MobileNetV2ReID:
         w, b = self.T["conv9"]
         x = self._relu6(F.conv2d(x, w, b))
         return x.float().mean(dim=(2, 3)).to(self.dtype)
-
-    def _forward(self, crops):
-        return self._forward_hip(crops) if self.hip else self._forward_torch(crops)
-
-    def __call__(self, crops):
-        torch = self.torch
-        with torch.no_grad():
-            n = crops.shape[0]
-            if n <= self.chunk:
-                return self._forward(crops)
-            return torch.cat([self._forward(crops[i:i + self.chunk])
-                              for i in range(0, n, self.chunk)])

@@ -37,6 +37,13 @@ except ImportError:   # pragma: no cover
     torch = None
 
 from .. import _lib
+from . import _backbone, clip, mlfn, mobilenetv2, osnet
+
+# The rebuilt backbone families as (module, class), in the order a weight file's name is tried
+# against them (each module's model_name): the OSNet family first (the trackers' default weights),
+# CLIP-ReID last (by the file's name alone).  tools/bench_osnet.py picks its class here as well.
+FAMILIES = ((osnet, osnet.OSNetReID), (mobilenetv2, mobilenetv2.MobileNetV2ReID),
+            (mlfn, mlfn.MLFNReID), (clip, clip.ClipReID))
 
 OUT_W, OUT_H = 128, 256   # cv2.resize(crop, (128, 256)) at :200-204
 
@@ -101,18 +108,13 @@ class ReIDDetectMultiBackend:
         self.lib = _lib.load_library()
         self.random_init = bool(random_init)
         if model is None and weights is not None:
-            model = self._build_osnet(weights)
+            model = self._build_backbone(weights)
         self.model = model
 
-    def _build_osnet(self, weights):
-        """reid_multibackend.py:57-80 as a dispatch on the weight file name: the OSNet family
-        first (the plain widths, the trackers' default weights, osnet_ibn_* and osnet_ain_*:
-        appearance/osnet.py VARIANTS), then MobileNetV2 (appearance/mobilenetv2.py VARIANTS),
-        then MLFN (appearance/mlfn.py VARIANTS), then CLIP-ReID (appearance/clip.py VARIANTS, by
-        the file's name alone)."""
-        from . import clip, mlfn, mobilenetv2, osnet
-        for family, cls in ((osnet, osnet.OSNetReID), (mobilenetv2, mobilenetv2.MobileNetV2ReID),
-                            (mlfn, mlfn.MLFNReID), (clip, clip.ClipReID)):
+    def _build_backbone(self, weights):
+        """reid_multibackend.py:57-80 as a dispatch on the weight file name: the first family of
+        FAMILIES whose VARIANTS hold a name that occurs in it."""
+        for family, cls in FAMILIES:
             name = family.model_name(weights)
             if name is not None:
                 break
@@ -125,7 +127,7 @@ class ReIDDetectMultiBackend:
                 "model=<torch module> for other networks")
         w = Path(weights)
         if w.is_file():
-            sd = osnet.load_checkpoint(w)
+            sd = _backbone.load_checkpoint(w)
         elif self.random_init:
             warnings.warn(f"ReID weights {str(w)!r} not on disk: {name} runs with fresh random "
                           "weights (random_init=True)", RuntimeWarning, stacklevel=3)

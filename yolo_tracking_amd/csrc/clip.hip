@@ -37,6 +37,7 @@
 // float32 or float16 storage, float32 arithmetic, no atomics.
 #include <algorithm>
 
+#include "by_storage.hpp"
 #include "common.hpp"
 #include "../../include/yolo_tracking_amd.h"
 
@@ -416,8 +417,7 @@ int yta_clip_linear(const void *x, long long x_stride, const void *w, long long 
     const int bytes = half ? 2 : 4;
     a.xvec = vec_ok(x, x_stride, K, bytes), a.wvec = vec_ok(w, w_stride, K, bytes);
     hipStream_t st = (hipStream_t)stream;
-    if (half) linear_launch<_Float16>(a, st);
-    else linear_launch<float>(a, st);
+    by_storage(half, [&](auto tag) { linear_launch<typename decltype(tag)::type>(a, st); });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -430,12 +430,11 @@ int yta_clip_layernorm(const void *x, long long x_stride, long long M, int C, co
               YTA_ERR_INVALID, "bad layer norm arguments (strides at least C)");
     const dim3 g((unsigned)((M + LY_T / 64 - 1) / (LY_T / 64)));
     hipStream_t st = (hipStream_t)stream;
-    if (half)
-        hipLaunchKernelGGL(k_layernorm<_Float16>, g, dim3(LY_T), 0, st, (const _Float16 *)x,
-                           x_stride, M, C, gamma, beta, eps, (_Float16 *)y, y_stride);
-    else
-        hipLaunchKernelGGL(k_layernorm<float>, g, dim3(LY_T), 0, st, (const float *)x, x_stride,
-                           M, C, gamma, beta, eps, (float *)y, y_stride);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_layernorm<T>, g, dim3(LY_T), 0, st, (const T *)x, x_stride, M, C,
+                           gamma, beta, eps, (T *)y, y_stride);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -446,12 +445,11 @@ int yta_clip_patches(const void *x, int N, int H, int W, int half, void *y, void
     const long long total = (long long)N * 3 * H * W, blocks = (total + 255) / 256;
     YTA_CHECK(blocks <= 0x7fffffffLL, YTA_ERR_INVALID, "grid too large");
     hipStream_t st = (hipStream_t)stream;
-    if (half)
-        hipLaunchKernelGGL(k_patches<_Float16>, dim3((unsigned)blocks), dim3(256), 0, st,
-                           (const _Float16 *)x, H, W, total, (_Float16 *)y);
-    else
-        hipLaunchKernelGGL(k_patches<float>, dim3((unsigned)blocks), dim3(256), 0, st,
-                           (const float *)x, H, W, total, (float *)y);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_patches<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T *)x, H,
+                           W, total, (T *)y);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -466,16 +464,12 @@ int yta_clip_tokens(const void *patches, long long patch_stride, const float *cl
     const long long rows = (long long)N * (G + 1), blocks = (rows + LY_T / 64 - 1) / (LY_T / 64);
     YTA_CHECK(blocks <= 0x7fffffffLL, YTA_ERR_INVALID, "grid too large");
     hipStream_t st = (hipStream_t)stream;
-    if (half)
-        hipLaunchKernelGGL(k_tokens<_Float16>, dim3((unsigned)blocks), dim3(LY_T), 0, st,
-                           (const _Float16 *)patches, patch_stride, class_embedding,
-                           positional_embedding, (long long)N, G, width, gamma, beta, eps,
-                           (_Float16 *)y);
-    else
-        hipLaunchKernelGGL(k_tokens<float>, dim3((unsigned)blocks), dim3(LY_T), 0, st,
-                           (const float *)patches, patch_stride, class_embedding,
-                           positional_embedding, (long long)N, G, width, gamma, beta, eps,
-                           (float *)y);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_tokens<T>, dim3((unsigned)blocks), dim3(LY_T), 0, st,
+                           (const T *)patches, patch_stride, class_embedding,
+                           positional_embedding, (long long)N, G, width, gamma, beta, eps, (T *)y);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -490,23 +484,18 @@ int yta_clip_attention(const void *qkv, int N, int L, int width, int head_dim, i
     const size_t lds = at_lds_bytes(L, half);
     const dim3 g((unsigned)((Lq + AT_QB - 1) / AT_QB), (unsigned)(width / AT_D), (unsigned)N);
     hipStream_t st = (hipStream_t)stream;
-    if (half) {
+    // the lambda returns the entry point's status: YTA_HIP leaves it on a failed attribute call
+    return by_storage(half, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
         if (lds > 65536)
-            YTA_HIP(hipFuncSetAttribute((const void *)k_attention<_Float16>,
+            YTA_HIP(hipFuncSetAttribute((const void *)k_attention<T>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)at_lds_bytes(AT_LMAX, 1)));
-        hipLaunchKernelGGL(k_attention<_Float16>, g, dim3(AT_T), lds, st, (const _Float16 *)qkv, L,
-                           Lq, width, (_Float16 *)y);
-    } else {
-        if (lds > 65536)
-            YTA_HIP(hipFuncSetAttribute((const void *)k_attention<float>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)at_lds_bytes(AT_LMAX, 0)));
-        hipLaunchKernelGGL(k_attention<float>, g, dim3(AT_T), lds, st, (const float *)qkv, L, Lq,
-                           width, (float *)y);
-    }
-    YTA_HIP(hipGetLastError());
-    return YTA_OK;
+                                        (int)at_lds_bytes(AT_LMAX, half)));
+        hipLaunchKernelGGL(k_attention<T>, g, dim3(AT_T), lds, st, (const T *)qkv, L, Lq, width,
+                           (T *)y);
+        YTA_HIP(hipGetLastError());
+        return YTA_OK;
+    });
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@
 // NCHW planes, float32 or float16 storage, float32 arithmetic, no atomics.
 #include <algorithm>
 
+#include "by_storage.hpp"
 #include "common.hpp"
 #include "../../include/yolo_tracking_amd.h"
 
@@ -283,12 +284,11 @@ int yta_mbv2_stem(const void *x, int N, int H, int W, const float *w, const floa
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const dim3 g((Wo + MS_TILE - 1) / MS_TILE, (Ho + MS_TILE - 1) / MS_TILE, N);
     YTA_CHECK(g.y <= 65535, YTA_ERR_INVALID, "grid too large");
-    if (half)
-        hipLaunchKernelGGL(k_mb_stem<_Float16>, g, dim3(256), 0, (hipStream_t)stream,
-                           (const _Float16 *)x, H, W, w, b, C0, (_Float16 *)y, Ho, Wo);
-    else
-        hipLaunchKernelGGL(k_mb_stem<float>, g, dim3(256), 0, (hipStream_t)stream,
-                           (const float *)x, H, W, w, b, C0, (float *)y, Ho, Wo);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_mb_stem<T>, g, dim3(256), 0, (hipStream_t)stream, (const T *)x, H, W,
+                           w, b, C0, (T *)y, Ho, Wo);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -306,17 +306,15 @@ int yta_mbv2_dw3x3(const void *x, const float *w, const float *b, int N, int C, 
     YTA_CHECK(blocks <= 0x7fffffffLL, YTA_ERR_INVALID, "grid too large");
     const dim3 g((unsigned)blocks);
     hipStream_t st = (hipStream_t)stream;
-#define YTA_MD_LAUNCH(T, L)                                                                     \
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+#define YTA_MD_LAUNCH(L)                                                                        \
     hipLaunchKernelGGL((k_mb_dw<T, L>), g, dim3(MD_T), 0, st, (const T *)x, w, b, C, H, W,      \
                        stride, Ho, Wo, ppb, planes, (T *)y)
-    if (half) {
-        if (lds) YTA_MD_LAUNCH(_Float16, true);
-        else YTA_MD_LAUNCH(_Float16, false);
-    } else {
-        if (lds) YTA_MD_LAUNCH(float, true);
-        else YTA_MD_LAUNCH(float, false);
-    }
+        if (lds) YTA_MD_LAUNCH(true);
+        else YTA_MD_LAUNCH(false);
 #undef YTA_MD_LAUNCH
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -338,12 +336,11 @@ int yta_mbv2_expand_dw(const void *x, const float *w1, const float *b1, const fl
     const dim3 grid((unsigned)tiles, chunks, N);
     const size_t lds = sizeof(float) * g.CT * 32 * (g.PTS + ME_SW);
     hipStream_t st = (hipStream_t)stream;
-    if (half)
-        hipLaunchKernelGGL(k_mb_expand_dw<_Float16>, grid, dim3(ME_T), lds, st,
-                           (const _Float16 *)x, w1, b1, wdw, b2, g, (_Float16 *)y);
-    else
-        hipLaunchKernelGGL(k_mb_expand_dw<float>, grid, dim3(ME_T), lds, st, (const float *)x, w1,
-                           b1, wdw, b2, g, (float *)y);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_mb_expand_dw<T>, grid, dim3(ME_T), lds, st, (const T *)x, w1, b1, wdw,
+                           b2, g, (T *)y);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }

@@ -26,6 +26,7 @@
 // NCHW planes, float32 or float16 storage, float32 arithmetic, no atomics.
 #include <algorithm>
 
+#include "by_storage.hpp"
 #include "common.hpp"
 #include "../../include/yolo_tracking_amd.h"
 
@@ -283,13 +284,11 @@ int yta_mlfn_gconv3x3(const void *x, const float *w, const float *b, const float
               YTA_ERR_INVALID, "grid too large");
     hipStream_t st = (hipStream_t)stream;
     const bool r4 = g.n <= 4;   // 4 accumulators where a group has no more channels
-    if (half) {
-        if (r4) gc_launch<_Float16, 4>(x, w, b, scale, g, N, y, st);
-        else gc_launch<_Float16, 8>(x, w, b, scale, g, N, y, st);
-    } else {
-        if (r4) gc_launch<float, 4>(x, w, b, scale, g, N, y, st);
-        else gc_launch<float, 8>(x, w, b, scale, g, N, y, st);
-    }
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (r4) gc_launch<T, 4>(x, w, b, scale, g, N, y, st);
+        else gc_launch<T, 8>(x, w, b, scale, g, N, y, st);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -307,14 +306,11 @@ int yta_mlfn_fsm(const void *pooled, int N, int cin, int f0, int f1, int G, cons
     const dim3 g((unsigned)((N + FS_SB - 1) / FS_SB));
     const size_t lds = sizeof(float) * (size_t)floats;
     hipStream_t st = (hipStream_t)stream;
-    if (half)
-        hipLaunchKernelGGL(k_fsm<_Float16>, g, dim3(FS_T), lds, st, (const _Float16 *)pooled, N,
-                           cin, f0, f1, G, w1, b1, w2, b2, w3, b3, sel, sel_stride,
-                           (_Float16 *)sel_t, sel_t_stride);
-    else
-        hipLaunchKernelGGL(k_fsm<float>, g, dim3(FS_T), lds, st, (const float *)pooled, N, cin, f0,
-                           f1, G, w1, b1, w2, b2, w3, b3, sel, sel_stride, (float *)sel_t,
-                           sel_t_stride);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_fsm<T>, g, dim3(FS_T), lds, st, (const T *)pooled, N, cin, f0, f1, G,
+                           w1, b1, w2, b2, w3, b3, sel, sel_stride, (T *)sel_t, sel_t_stride);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -328,12 +324,11 @@ int yta_mlfn_subsample(const void *x, int N, int C, int H, int W, int stride, in
     const long long total = (long long)N * C * Ho * Wo, blocks = (total + 255) / 256;
     YTA_CHECK(blocks <= 0x7fffffffLL, YTA_ERR_INVALID, "grid too large");
     hipStream_t st = (hipStream_t)stream;
-    if (half)
-        hipLaunchKernelGGL(k_subsample<_Float16>, dim3((unsigned)blocks), dim3(256), 0, st,
-                           (const _Float16 *)x, H, W, stride, Ho, Wo, total, (_Float16 *)y);
-    else
-        hipLaunchKernelGGL(k_subsample<float>, dim3((unsigned)blocks), dim3(256), 0, st,
-                           (const float *)x, H, W, stride, Ho, Wo, total, (float *)y);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_subsample<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T *)x,
+                           H, W, stride, Ho, Wo, total, (T *)y);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -344,12 +339,11 @@ int yta_mlfn_mean2(const void *a, const void *b, long long count, int half, void
               "bad mean arguments");
     const dim3 g((unsigned)((count + 255) / 256));
     hipStream_t st = (hipStream_t)stream;
-    if (half)
-        hipLaunchKernelGGL(k_mean2<_Float16>, g, dim3(256), 0, st, (const _Float16 *)a,
-                           (const _Float16 *)b, count, (_Float16 *)y);
-    else
-        hipLaunchKernelGGL(k_mean2<float>, g, dim3(256), 0, st, (const float *)a,
-                           (const float *)b, count, (float *)y);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_mean2<T>, g, dim3(256), 0, st, (const T *)a, (const T *)b, count,
+                           (T *)y);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }

@@ -29,6 +29,7 @@
 // NCHW planes, float32 or float16 storage, float32 arithmetic.
 #include <algorithm>
 
+#include "by_storage.hpp"
 #include "common.hpp"
 #include "../../include/yolo_tracking_amd.h"
 
@@ -614,12 +615,11 @@ static int stem_launch(const void *x, int N, int H, int W, const float *w, const
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const dim3 g((Wo + ST_TILE - 1) / ST_TILE, (Ho + ST_TILE - 1) / ST_TILE, N);
     const size_t lds = sizeof(float) * 147 * C0;
-    if (half)
-        hipLaunchKernelGGL((k_stem<_Float16, 16, RELU>), g, dim3(256), lds, (hipStream_t)stream,
-                           (const _Float16 *)x, H, W, w, b, C0, (_Float16 *)y, Ho, Wo);
-    else
-        hipLaunchKernelGGL((k_stem<float, 16, RELU>), g, dim3(256), lds, (hipStream_t)stream,
-                           (const float *)x, H, W, w, b, C0, (float *)y, Ho, Wo);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((k_stem<T, 16, RELU>), g, dim3(256), lds, (hipStream_t)stream,
+                           (const T *)x, H, W, w, b, C0, (T *)y, Ho, Wo);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -660,29 +660,23 @@ int yta_osnet_dw3x3(const void *x, long long x_n_stride, long long x_c_stride, c
     if (H * W <= DW_LDS_PX) {
         const int ppb = std::max(1, std::min(C, DW_LDS_PX / (H * W)));
         const dim3 gl((C + ppb - 1) / ppb, N);
-        if (half)
-            hipLaunchKernelGGL(k_dw3x3_lds<_Float16>, gl, dim3(DW_T), 0, (hipStream_t)stream,
-                               (const _Float16 *)x, x_n_stride, x_c_stride, w, b, C, H, W, ppb,
-                               (_Float16 *)y_first, yf_n_stride, n_first, (_Float16 *)y_rest,
-                               yr_n_stride, plane_sum, ps_n_stride);
-        else
-            hipLaunchKernelGGL(k_dw3x3_lds<float>, gl, dim3(DW_T), 0, (hipStream_t)stream,
-                               (const float *)x, x_n_stride, x_c_stride, w, b, C, H, W, ppb,
-                               (float *)y_first, yf_n_stride, n_first, (float *)y_rest,
-                               yr_n_stride, plane_sum, ps_n_stride);
+        by_storage(half, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL(k_dw3x3_lds<T>, gl, dim3(DW_T), 0, (hipStream_t)stream,
+                               (const T *)x, x_n_stride, x_c_stride, w, b, C, H, W, ppb,
+                               (T *)y_first, yf_n_stride, n_first, (T *)y_rest, yr_n_stride,
+                               plane_sum, ps_n_stride);
+        });
         YTA_HIP(hipGetLastError());
         return YTA_OK;
     }
     const dim3 g(C, N);
-    if (half)
-        hipLaunchKernelGGL(k_dw3x3<_Float16>, g, dim3(DW_T), 0, (hipStream_t)stream,
-                           (const _Float16 *)x, x_n_stride, x_c_stride, w, b, C, H, W,
-                           (_Float16 *)y_first, yf_n_stride, n_first, (_Float16 *)y_rest,
-                           yr_n_stride, plane_sum, ps_n_stride);
-    else
-        hipLaunchKernelGGL(k_dw3x3<float>, g, dim3(DW_T), 0, (hipStream_t)stream, (const float *)x,
-                           x_n_stride, x_c_stride, w, b, C, H, W, (float *)y_first, yf_n_stride,
-                           n_first, (float *)y_rest, yr_n_stride, plane_sum, ps_n_stride);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_dw3x3<T>, g, dim3(DW_T), 0, (hipStream_t)stream, (const T *)x,
+                           x_n_stride, x_c_stride, w, b, C, H, W, (T *)y_first, yf_n_stride,
+                           n_first, (T *)y_rest, yr_n_stride, plane_sum, ps_n_stride);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -691,12 +685,11 @@ int yta_osnet_gate_sum(const void *stack, const void *gate, int N, int C, int P,
                        void *out, void *stream) {
     YTA_CHECK(stack && gate && out && N > 0 && C > 0 && P > 0, YTA_ERR_INVALID, "bad argument");
     const dim3 g(C, N);
-    if (half)
-        hipLaunchKernelGGL(k_gate_sum<_Float16>, g, dim3(256), 0, (hipStream_t)stream,
-                           (const _Float16 *)stack, (const _Float16 *)gate, C, P, (_Float16 *)out);
-    else
-        hipLaunchKernelGGL(k_gate_sum<float>, g, dim3(256), 0, (hipStream_t)stream,
-                           (const float *)stack, (const float *)gate, C, P, (float *)out);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_gate_sum<T>, g, dim3(256), 0, (hipStream_t)stream, (const T *)stack,
+                           (const T *)gate, C, P, (T *)out);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -712,15 +705,12 @@ int yta_osnet_pointwise(const yta_pw_args *args, int half, void *stream) {
                  a.G * ((mt + MB - 1) / MB), a.N);
     YTA_CHECK(g.y <= 65535 && g.z <= 65535, YTA_ERR_INVALID, "grid too large");
     hipStream_t st = (hipStream_t)stream;
-    if (half) {
-        if (MB == 1) hipLaunchKernelGGL((k_pw<_Float16, 1>), g, dim3(PW_T), 0, st, a);
-        else if (MB == 2) hipLaunchKernelGGL((k_pw<_Float16, 2>), g, dim3(PW_T), 0, st, a);
-        else hipLaunchKernelGGL((k_pw<_Float16, 4>), g, dim3(PW_T), 0, st, a);
-    } else {
-        if (MB == 1) hipLaunchKernelGGL((k_pw<float, 1>), g, dim3(PW_T), 0, st, a);
-        else if (MB == 2) hipLaunchKernelGGL((k_pw<float, 2>), g, dim3(PW_T), 0, st, a);
-        else hipLaunchKernelGGL((k_pw<float, 4>), g, dim3(PW_T), 0, st, a);
-    }
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (MB == 1) hipLaunchKernelGGL((k_pw<T, 1>), g, dim3(PW_T), 0, st, a);
+        else if (MB == 2) hipLaunchKernelGGL((k_pw<T, 2>), g, dim3(PW_T), 0, st, a);
+        else hipLaunchKernelGGL((k_pw<T, 4>), g, dim3(PW_T), 0, st, a);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -744,18 +734,14 @@ int yta_osnet_instnorm(const void *x, const void *res, const float *gamma, const
     const long long planes = (long long)N * C;
     YTA_CHECK(planes <= 0x7fffffffLL, YTA_ERR_INVALID, "grid too large");
     hipStream_t st = (hipStream_t)stream;
-    if (P <= IN_RESIDENT_PX) {
-        if (half) instnorm_launch<_Float16, false>(x, res, gamma, beta, planes, C, P, relu, y, 1, P, st);
-        else instnorm_launch<float, false>(x, res, gamma, beta, planes, C, P, relu, y, 1, P, st);
-    } else if (half) {
-        hipLaunchKernelGGL(k_instnorm_loop<_Float16>, dim3((unsigned)planes), dim3(IN_T), 0, st,
-                           (const _Float16 *)x, (const _Float16 *)res, gamma, beta, C, P, relu,
-                           (_Float16 *)y);
-    } else {
-        hipLaunchKernelGGL(k_instnorm_loop<float>, dim3((unsigned)planes), dim3(IN_T), 0, st,
-                           (const float *)x, (const float *)res, gamma, beta, C, P, relu,
-                           (float *)y);
-    }
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (P <= IN_RESIDENT_PX)
+            instnorm_launch<T, false>(x, res, gamma, beta, planes, C, P, relu, y, 1, P, st);
+        else
+            hipLaunchKernelGGL(k_instnorm_loop<T>, dim3((unsigned)planes), dim3(IN_T), 0, st,
+                               (const T *)x, (const T *)res, gamma, beta, C, P, relu, (T *)y);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -774,8 +760,10 @@ int yta_osnet_instnorm_maxpool(const void *x, const float *gamma, const float *b
         return rc != YTA_OK ? rc : yta_osnet_pool(work, N, C, H, W, 0, half, y, stream);
     }
     hipStream_t st = (hipStream_t)stream;
-    if (half) instnorm_launch<_Float16, true>(x, nullptr, gamma, beta, planes, C, P, 1, y, H, W, st);
-    else instnorm_launch<float, true>(x, nullptr, gamma, beta, planes, C, P, 1, y, H, W, st);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        instnorm_launch<T, true>(x, nullptr, gamma, beta, planes, C, P, 1, y, H, W, st);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -787,12 +775,11 @@ int yta_osnet_pool(const void *x, int N, int C, int H, int W, int kind, int half
     const int Ho = kind == 0 ? (H - 1) / 2 + 1 : H / 2, Wo = kind == 0 ? (W - 1) / 2 + 1 : W / 2;
     YTA_CHECK(kind == 2 || (Ho > 0 && Wo > 0), YTA_ERR_INVALID, "plane too small");
     const dim3 g(C, N);
-    if (half)
-        hipLaunchKernelGGL(k_pool<_Float16>, g, dim3(256), 0, (hipStream_t)stream,
-                           (const _Float16 *)x, C, H, W, kind, (_Float16 *)y, Ho, Wo);
-    else
-        hipLaunchKernelGGL(k_pool<float>, g, dim3(256), 0, (hipStream_t)stream, (const float *)x, C,
-                           H, W, kind, (float *)y, Ho, Wo);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_pool<T>, g, dim3(256), 0, (hipStream_t)stream, (const T *)x, C, H, W,
+                           kind, (T *)y, Ho, Wo);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
@@ -804,14 +791,12 @@ int yta_osnet_gate(const float *plane_sum, int N, int mid, int hid, int P, const
                   hid > 0 && hid <= 64 && P > 0,
               YTA_ERR_INVALID, "bad gate arguments");
     const float inv = 1.0f / (float)P;
-    if (half)
-        hipLaunchKernelGGL(k_gate<_Float16>, dim3(N), dim3(256), 0, (hipStream_t)stream, plane_sum,
-                           inv, (const _Float16 *)w1, (const _Float16 *)b1, (const _Float16 *)w2,
-                           (const _Float16 *)b2, mid, hid, (_Float16 *)gate);
-    else
-        hipLaunchKernelGGL(k_gate<float>, dim3(N), dim3(256), 0, (hipStream_t)stream, plane_sum,
-                           inv, (const float *)w1, (const float *)b1, (const float *)w2,
-                           (const float *)b2, mid, hid, (float *)gate);
+    by_storage(half, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_gate<T>, dim3(N), dim3(256), 0, (hipStream_t)stream, plane_sum, inv,
+                           (const T *)w1, (const T *)b1, (const T *)w2, (const T *)b2, mid, hid,
+                           (T *)gate);
+    });
     YTA_HIP(hipGetLastError());
     return YTA_OK;
 }
