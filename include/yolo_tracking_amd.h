@@ -1187,6 +1187,41 @@ int yta_mlfn_subsample(const void *x, int N, int C, int H, int W, int stride, in
 int yta_mlfn_mean2(const void *a, const void *b, long long count, int half, void *y,
                    void *stream);
 
+/* ---- LMBN-n (boxmot/appearance/backbones/lmbn/lmbn_n.py, lmbn/bnneck.py; appearance/lmbn.py).
+ * The conventions of the MLFN section: device pointers, asynchronous on `stream`, float32
+ * (half = 0) or float16 (half = 1) storage, float32 arithmetic, BatchNorms folded into float32
+ * weights and biases, no atomics (the same input gives the same bits).  The trunk, the three
+ * branches and the bottleneck behind the global branch are OSNet x1.0 layers (yta_osnet_*).
+ * yta_lmbn_pool: the pooling stage (lmbn_n.py:98-105) in one read of x N x C x H x W: per
+ * (n, c) plane its maximum, its mean, and the means of AdaptiveAvgPool2d((2, 1))'s two bins,
+ * rows [0, ceil(H / 2)) and [floor(H / 2), H) (an odd H puts the middle row into both; H = 1 makes
+ * both row 0), each to its own N x C output in the storage type.  An output that is NULL is
+ * neither computed into nor touched; at least one must be given.  The maximum starts from the
+ * plane's first element (planes may be negative throughout) and is exact in both storage types.
+ * yta_lmbn_neck: the seven heads (:107-120) and torch.stack(dim=2).flatten(1, 2) (:127-131) in
+ * one launch.  heads: YTA_LMBN_HEADS descriptors in host memory (copied before the call returns).
+ * Head j reads N rows of K_j values in the storage type, row n at x + n * x_stride elements
+ * (x_stride >= K; two heads may read two halves of one buffer), and writes
+ *   y[n * 7 C + c * 7 + j] = act(sum_k w[k * C + c] x[n][k] + bias[c]),   c < C,
+ * w float32 K x C (k-major, as yta_osnet_pointwise takes it; heads may share one), bias float32 C
+ * or NULL; act: relu != 0 clamps at 0 first, then, where scale or shift is given (float32 C, a
+ * missing one is 1 or 0), v * scale[c] + shift[c]: a BatchNorm that follows the ReLU
+ * (reduction_ch_*.bn behind `shared`) and cannot fold into w.  N, C and every K are arbitrary
+ * (> 0); N at most 65535 * 32. */
+#define YTA_LMBN_HEADS 7
+typedef struct yta_lmbn_head {
+    const void *x;
+    long long x_stride;
+    const float *w;
+    const float *bias;
+    const float *scale;
+    const float *shift;
+    int K, relu;
+} yta_lmbn_head;
+int yta_lmbn_pool(const void *x, int N, int C, int H, int W, int half, void *mx, void *mean,
+                  void *upper, void *lower, void *stream);
+int yta_lmbn_neck(const yta_lmbn_head *heads, int N, int C, int half, void *y, void *stream);
+
 /* ---- CLIP-ReID ViT (boxmot/appearance/backbones/clip/clip/model.py VisionTransformer,
  * make_model.py:96-122; appearance/clip.py).  Device pointers, asynchronous on `stream`, float32
  * (half = 0) or float16 (half = 1) storage, float32 arithmetic, no atomics (the same input gives

@@ -11,7 +11,11 @@ NHWC and NCHW ("hip_blocks": false), the baseline a model=<torch module> user ge
 --variant mlfn (appearance/mlfn.py) measures the MLFN HIP forward against the same folded graph on
 PyTorch's kernels (hip=False, "hip_blocks": false) on the same device, float32 and float16.
 --variant clip (appearance/clip.py) does the same for the CLIP-ReID ViT-B/16, in chunks of
-appearance.clip.CHUNK crops."""
+appearance.clip.CHUNK crops.
+--variant lmbn_n (appearance/lmbn.py) measures the LMBN-n HIP forward with the fused neck (one
+yta_lmbn_neck launch, "fused": true), with the unfused neck (seven yta_osnet_pointwise launches
+and the channel heads' affine, "fused": false), and the folded graph on PyTorch's kernels
+("hip_blocks": false), float32 and float16."""
 import argparse
 import json
 import os
@@ -30,7 +34,7 @@ def main():
     ap.add_argument("--variant", default="osnet_x0_25",
                     choices=[v for family, _ in FAMILIES for v in sorted(family.VARIANTS)],
                     help="OSNet variant (plain, osnet_ibn_* or osnet_ain_*; default osnet_x0_25) "
-                         "or mobilenetv2_x1_0 / mobilenetv2_x1_4, or mlfn, or clip")
+                         "or mobilenetv2_x1_0 / mobilenetv2_x1_4, or mlfn, or lmbn_n, or clip")
     ap.add_argument("--crops", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=10)
     args = ap.parse_args()
@@ -38,7 +42,7 @@ def main():
     from yolo_tracking_amd.appearance import ReIDDetectMultiBackend
     from yolo_tracking_amd.appearance.clip import CHUNK as CLIP_CHUNK
     family, cls = next(f for f in FAMILIES if args.variant in f[0].VARIANTS)
-    kind = family.__name__.rsplit(".", 1)[1]   # osnet, mobilenetv2, mlfn or clip
+    kind = family.__name__.rsplit(".", 1)[1]   # osnet, mobilenetv2, mlfn, lmbn or clip
     rng = np.random.default_rng(0)
     H, W, n = 1080, 1920, args.crops
     img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
@@ -53,6 +57,10 @@ def main():
     elif kind == "mlfn":   # the HIP forward and the folded graph on PyTorch's kernels, NCHW
         label = "MLFN"
         configs = [(half, 1024, hip, False, None) for half in (False, True) for hip in (True, False)]
+    elif kind == "lmbn":   # the fused and the unfused neck, and the graph on PyTorch's kernels
+        label = "LMBN"
+        configs = [(half, 1024, hip, not hip, fused) for half in (False, True)
+                   for hip, fused in ((True, True), (True, False), (False, None))]
     elif kind == "mobilenetv2":
         label = "MobileNetV2"
         configs = [(half, 1024, hip, cl, fused) for half in (False, True)
@@ -68,6 +76,10 @@ def main():
         extra = {"channels_last": cl} if kind in ("osnet", "mobilenetv2") else {}
         if kind == "mobilenetv2":
             extra["fused"] = bool(fused)
+        if kind == "lmbn":
+            extra = {"channels_last": cl}
+            if hip:
+                extra["fused_neck"] = bool(fused)
         net = cls(args.variant, None, device="cuda:0", half=half, chunk=chunk, hip=hip, **extra)
         reid = ReIDDetectMultiBackend(None, device=0, fp16=half, model=net)
         crops = reid.preprocess(boxes, img)

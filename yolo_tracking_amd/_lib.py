@@ -27,6 +27,15 @@ class PwArgs(ctypes.Structure):
                 ("relu", ctypes.c_int), ("pad", ctypes.c_int)]
 
 
+class LmbnHead(ctypes.Structure):
+    """yta_lmbn_head (include/yolo_tracking_amd.h): one head of yta_lmbn_neck."""
+    _fields_ = [("x", ctypes.c_void_p), ("x_stride", ctypes.c_longlong), ("w", ctypes.c_void_p),
+                ("bias", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p),
+                ("K", ctypes.c_int), ("relu", ctypes.c_int)]
+
+
+LMBN_HEADS = 7   # YTA_LMBN_HEADS
+
 YTA_OK = 0
 YTA_ERR_INVALID = -1
 YTA_ERR_HIP = -2
@@ -301,6 +310,8 @@ _SIGS = {
                       _P, ctypes.c_longlong, _P], _I),
     "yta_mlfn_subsample": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], _I),
     "yta_mlfn_mean2": ([_P, _P, ctypes.c_longlong, _I, _P, _P], _I),
+    "yta_lmbn_pool": ([_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P], _I),
+    "yta_lmbn_neck": ([_P, _I, _I, _I, _P, _P], _I),
     "yta_clip_linear": ([_P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong,
                          _I, _I, _I, _I, _I, _P, ctypes.c_longlong, _P], _I),
     "yta_clip_layernorm": ([_P, ctypes.c_longlong, ctypes.c_longlong, _I, _P, _P, ctypes.c_float,

@@ -1,4 +1,4 @@
-"""The driver layer the ReID backbones share (osnet.py, mobilenetv2.py, mlfn.py, clip.py).
+"""The driver layer the ReID backbones share (osnet.py, mobilenetv2.py, mlfn.py, lmbn.py, clip.py).
 
 Each backbone is an eval-mode inference graph built from a checkpoint in the reference's key layout:
 BatchNorms are folded on the host in float64 (bn_affine, fold_bn), parameters are cast once to the
@@ -138,7 +138,7 @@ class Kernels:
 
 
 class ReIDBackbone:
-    """What the four *ReID classes (and the single-block graphs of MLFN and CLIP) share: the
+    """What the *ReID classes (and the single-block graphs of MLFN and CLIP) share: the
     device / hip / storage type / chunk setup, the chunked call and the dispatch between the HIP
     forward and the same graph on PyTorch's operators."""
 

@@ -301,6 +301,16 @@ class OSNetReID(ReIDBackbone):
             out = F.instance_norm(out, weight=blk.inorm[0], bias=blk.inorm[1], eps=IN_EPS)
         return F.relu(out)
 
+    def _blocks_torch(self, x, blocks):
+        """A run of omni-scale blocks and transitions (what _build leaves in self.blocks)."""
+        F = self.torch.nn.functional
+        for blk in blocks:
+            if isinstance(blk, _Reduce):
+                x = F.avg_pool2d(F.relu(F.conv2d(x, blk.w, blk.b)), 2, stride=2)
+            else:
+                x = self._os_block(x, blk)
+        return x
+
     def _forward_torch(self, crops):
         F = self.torch.nn.functional
         x = crops.to(self.device, self.dtype).contiguous(memory_format=self.fmt)
@@ -310,11 +320,7 @@ class OSNetReID(ReIDBackbone):
             g, bt = self.P["stem_norm"][:2]
             x = F.instance_norm(x, weight=g, bias=bt, eps=IN_EPS)
         x = F.max_pool2d(F.relu(x), 3, stride=2, padding=1)
-        for blk in self.blocks:
-            if isinstance(blk, _Reduce):
-                x = F.avg_pool2d(F.relu(F.conv2d(x, blk.w, blk.b)), 2, stride=2)
-            else:
-                x = self._os_block(x, blk)
+        x = self._blocks_torch(x, self.blocks)
         w, b = self.P["conv5"]
         x = F.relu(F.conv2d(x, w, b))
         v = x.float().mean(dim=(2, 3)).to(self.dtype)
@@ -377,6 +383,20 @@ class OSNetReID(ReIDBackbone):
                     out.data_ptr())
         return out
 
+    def _blocks_hip(self, x, blocks):
+        """_blocks_torch in HIP: a transition is its 1x1 GEMM + ReLU and the 2x2 average pool."""
+        K = self.K
+        n = x.shape[0]
+        for blk in blocks:
+            if isinstance(blk, _Reduce):
+                c, h, w = x.shape[1:]
+                cr = blk.wk.shape[2]
+                y = K.pw(x, blk.wk, blk.bk, k1=c, cout_g=cr, P=h * w, N=n, relu=True)
+                x = K.pool(y.view(n, cr, h, w), 1)
+            else:
+                x = self._os_block_hip(x, blk)
+        return x
+
     def _forward_hip(self, crops):
         K = self.K
         x = crops.to(self.device, self.dtype).contiguous()
@@ -393,14 +413,7 @@ class OSNetReID(ReIDBackbone):
             K.call("yta_osnet_instnorm_maxpool", stem.data_ptr(), pair[2].data_ptr(),
                    pair[3].data_ptr(), n, c0, sh, sw, K.half,
                    work.data_ptr() if work is not None else None, x.data_ptr())
-        for blk in self.blocks:
-            if isinstance(blk, _Reduce):
-                c, h, w = x.shape[1:]
-                cr = blk.wk.shape[2]
-                y = K.pw(x, blk.wk, blk.bk, k1=c, cout_g=cr, P=h * w, N=n, relu=True)
-                x = K.pool(y.view(n, cr, h, w), 1)
-            else:
-                x = self._os_block_hip(x, blk)
+        x = self._blocks_hip(x, self.blocks)
         w5, b5 = self.H["conv5"]
         c, h, w = x.shape[1:]
         y = K.pw(x, w5, b5, k1=c, cout_g=w5.shape[2], P=h * w, N=n, relu=True)

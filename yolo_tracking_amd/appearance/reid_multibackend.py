@@ -16,9 +16,13 @@ channels-last, batched branches) built from `weights` as the reference builds it
 file name (reid_multibackend.py:57-80): osnet_x0_25 .. osnet_x1_0, and the instance-norm members
 of the family, osnet_ibn_x1_0 and osnet_ain_x1_0 (and their narrower widths), whose norms run in
 csrc/osnet.hip as well, or MobileNetV2 (appearance/mobilenetv2.py: mobilenetv2_x1_0 and
-mobilenetv2_x1_4, csrc/mbv2.hip), or MLFN (appearance/mlfn.py: mlfn, csrc/mlfn.hip), or the
-CLIP-ReID ViT-B/16 (appearance/clip.py: clip, csrc/clip.hip; 1280 features); the
-reference's .pt state dicts load unchanged (torch.load(weights_only=True)).  A weight file that is not on disk would be
+mobilenetv2_x1_4, csrc/mbv2.hip), or MLFN (appearance/mlfn.py: mlfn, csrc/mlfn.hip), or LMBN-n
+(appearance/lmbn.py: lmbn_n, OSNet x1.0 layers in three branches and a seven-head neck,
+csrc/lmbn.hip; 3584 features), or the CLIP-ReID ViT-B/16 (appearance/clip.py: clip,
+csrc/clip.hip; 1280 features); the reference's .pt state dicts load unchanged
+(torch.load(weights_only=True)); an LMBN-n checkpoint's tensors are what runs, where the
+reference never reads them (appearance/lmbn.py).  ResNet-50 / ResNet-101 and HA-CNN are not
+rebuilt.  A weight file that is not on disk would be
 downloaded by the reference (gdown, :61-64) or end the program (:67-72); there is no network here,
 so a missing file raises FileNotFoundError.  Freshly initialised weights (benchmarks, plumbing
 tests) are an explicit opt-in: `random_init=True`.  `model=` (any torch module on the device
@@ -37,13 +41,14 @@ except ImportError:   # pragma: no cover
     torch = None
 
 from .. import _lib
-from . import _backbone, clip, mlfn, mobilenetv2, osnet
+from . import _backbone, clip, lmbn, mlfn, mobilenetv2, osnet
 
 # The rebuilt backbone families as (module, class), in the order a weight file's name is tried
 # against them (each module's model_name): the OSNet family first (the trackers' default weights),
-# CLIP-ReID last (by the file's name alone).  tools/bench_osnet.py picks its class here as well.
+# LMBN-n and CLIP-ReID last (by the file's name alone).  tools/bench_osnet.py picks its class here
+# as well.
 FAMILIES = ((osnet, osnet.OSNetReID), (mobilenetv2, mobilenetv2.MobileNetV2ReID),
-            (mlfn, mlfn.MLFNReID), (clip, clip.ClipReID))
+            (mlfn, mlfn.MLFNReID), (lmbn, lmbn.LMBNReID), (clip, clip.ClipReID))
 
 OUT_W, OUT_H = 128, 256   # cv2.resize(crop, (128, 256)) at :200-204
 
@@ -122,8 +127,8 @@ class ReIDDetectMultiBackend:
             raise NotImplementedError(
                 f"ReID weights {str(weights)!r}: only the OSNet family (osnet_x0_25 .. osnet_x1_0, "
                 "osnet_ibn_x1_0, osnet_ain_x1_0 and their other widths), MobileNetV2 "
-                "(mobilenetv2_x1_0, mobilenetv2_x1_4), MLFN (mlfn) and the CLIP-ReID ViT-B/16 "
-                "(clip) are rebuilt on the MI355X path; pass "
+                "(mobilenetv2_x1_0, mobilenetv2_x1_4), MLFN (mlfn), LMBN-n (lmbn_n) and the "
+                "CLIP-ReID ViT-B/16 (clip) are rebuilt on the MI355X path; pass "
                 "model=<torch module> for other networks")
         w = Path(weights)
         if w.is_file():
